@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """Quorum-decision throughput of the MI355X batched quorum engine (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2tl|c2t|c3mt|c4t|...] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2tl|c2t|c3mt|c4t|...]
+                    [--dump-outputs DIR] [--full [--no-cpu] [--extra LEGS]]
+
+A plain run sets up, warms up through the timed path (W steps, and at least one pass over every
+batch), times one window of K steps and prints the result line. --full adds everything else: three timed windows (the median reported) with the other
+ways of running the same steps beside them, the full-size oracle check, the CPU baseline and the
+extra legs. --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.
 
 A step is one pass of the hot path over one batch of synthetic groups resident in HBM: for the
 headline workload (BASELINE configs[1], "c2tl") one hq_commit_dev launch over 1,048,576 groups x 3
@@ -170,6 +176,57 @@ def decisions_per_group(w):
 
 def log(msg):
     print(msg, file=sys.stderr, flush=True)
+
+
+DUMP_LIMIT_BYTES = 60 * 1000 * 1000    # --dump-outputs: every file of one run together
+
+
+def unpack_bits(words, count, width=1):
+    """Per-group values of a packed output column (little-endian bit order, `width` bits per
+    group, 64 // width groups per u64 word) as uint8[count]."""
+    bits = np.unpackbits(words.view(np.uint8), bitorder="little")[:count * width]
+    if width == 1:
+        return bits
+    return (bits.reshape(count, width) << np.arange(width, dtype=np.uint8)).sum(
+        axis=1, dtype=np.uint8)
+
+
+def dump_outputs(path, arrays, rank=0, world=1):
+    """--dump-outputs: the last timed step's outputs, one DIR/<name>.npy per array, float64 for
+    the index columns and float32 for the per-group bits and codes (both exact). Above
+    DUMP_LIMIT_BYTES in all, every array keeps the same fraction of its elements, picked by a
+    generator with a fixed seed (the same elements in every run)."""
+    os.makedirs(path, exist_ok=True)
+    conv = {name: a.astype(np.float32 if a.dtype.itemsize == 1 else np.float64)
+            for name, a in arrays.items()}
+    total = sum(a.nbytes for a in conv.values())
+    for name, a in conv.items():
+        if total > DUMP_LIMIT_BYTES:
+            keep = int(len(a) * DUMP_LIMIT_BYTES / total)
+            idx = np.sort(np.random.default_rng(SEED_BASE).choice(len(a), keep, replace=False))
+            a = a[idx]
+        np.save(os.path.join(path, (f"rank{rank}_" if world > 1 else "") + name + ".npy"), a)
+
+
+def step_outputs(ctx, w, bufs):
+    """What a caller of the timed path receives from one step, downloaded from its batch set
+    `bufs` (a build_sets entry): {name: numpy array, one value per group}."""
+    out = {}
+    if w["kind"] in ("commit", "lag"):
+        for b in bufs:
+            sfx = f"_n{b.n_max}" if len(bufs) > 1 else ""
+            fb = unpack_bits(ctx.download(b.fallback), b.G)
+            if w["kind"] == "lag":     # a fallback group's cout_lag is not a decision: 0 here
+                out["cout_lag" + sfx] = np.where(fb != 0, 0, ctx.download(b.cout_lag))
+            else:
+                out["committed" + sfx] = ctx.download(b.committed_out)
+            out["changed" + sfx] = unpack_bits(ctx.download(b.changed), b.G)
+            out["fallback" + sfx] = fb
+    else:
+        _, conf, outc, _ = bufs
+        out["confirmed"] = unpack_bits(ctx.download(conf), w["G"])
+        out["outcome"] = unpack_bits(ctx.download(outc), w["G"], 2)
+    return out
 
 
 class Dist:
@@ -422,7 +479,9 @@ def groups_per_step(w):
     return (w["G"] // 3) * 3 if w["kind"] in ("commit", "lag") and w["mixed"] else w["G"]
 
 
-def run_gpu(w, steps, warmup, d: Dist):
+def run_gpu(w, steps, warmup, d: Dist, full=True, dump=None):
+    """full=False (a plain headline run): no second pass over set 0 for the parity check and no
+    result gather. dump: the --dump-outputs directory."""
     from dragonboat_amd import hipquorum as hq
     from dragonboat_amd import shard
 
@@ -523,10 +582,13 @@ def run_gpu(w, steps, warmup, d: Dist):
                     avg_kernel_s * 1e6, achieved_local]]
     # node-level roofline: every GPU's achieved bytes/s over N x the peak
     achieved_node = d.sum(achieved_local)
+    if dump:
+        dump_outputs(dump, step_outputs(ctx, w, sets[(first + steps - 1) % nsets]), d.rank,
+                     d.world)
     # The decisions of set 0, taken once more after the timed region, for the full-size parity
     # check of the cpu_baseline leg (every bucket of the step; outputs only, no timing).
     set0 = None
-    if w["kind"] in ("commit", "lag"):
+    if full and w["kind"] in ("commit", "lag"):
         if w["kind"] == "commit" and w["mixed"] and not w.get("separate"):
             ctx.commit_fused_dev(per_step[0])
         else:
@@ -539,7 +601,7 @@ def run_gpu(w, steps, warmup, d: Dist):
             set0.append(dict(n=n, cid_base=rng.cid_base, cid_stride=rng.cid_stride,
                              count=rng.count, out=[ctx.download(a) for a in outs]))
     gather = None
-    if d.world > 1 and w["kind"] == "commit" and not w["mixed"]:
+    if full and d.world > 1 and w["kind"] == "commit" and not w["mixed"]:
         # optional result gather: every GPU's changed bits of batch 0 to every
         # rank, in clusterID order; off the timed region
         try:
@@ -577,7 +639,8 @@ def fused_chunks(steps):
     return [(bounds[i], bounds[i + 1] - bounds[i]) for i in range(n)]
 
 
-def run_engine(w, steps, warmup, d: Dist, windows=3, headline="fused", share=1):
+def run_engine(w, steps, warmup, d: Dist, windows=3, headline="fused", share=1, full=True,
+               dump=None):
     """A commit workload stepped through the persistent commit engine (hq_engine_*,
     dragonboat_amd/csrc/hq_engine.hip): per timed window the K steps are posted one hq_engine_post call each
     (post-as-ready, the reference's step-worker shape) and decided by ONE resident launch (no
@@ -593,7 +656,12 @@ def run_engine(w, steps, warmup, d: Dist, windows=3, headline="fused", share=1):
     workers' batches of a step (16 step workers in the reference, internal/settings/hard.go:35,
     execengine.go:675-690). headline "engine": the resident engine's windows. share: the ranks
     on this GPU; above 1 each engine is capped at its share of the full grid (max_workgroups), so
-    that the co-located engines are all resident."""
+    that the co-located engines are all resident.
+
+    full=False (a plain run): only the headline's own mode is warmed up (through that mode, over
+    `warmup` steps and at least once over every batch) and timed, and set 0 is not decided again
+    for the parity check. dump: the --dump-outputs
+    directory, written from the last timed step's batch right after the last window."""
     from dragonboat_amd import hipquorum as hq
     from dragonboat_amd import shard
 
@@ -601,35 +669,59 @@ def run_engine(w, steps, warmup, d: Dist, windows=3, headline="fused", share=1):
     sets, per_set = build_sets(ctx, hq, shard, w, d)
     nsets = len(sets)
     lay = hq.HQ_LAYOUT_TILES_LEADER if w.get("lead") else hq.HQ_LAYOUT_TILES
+    hm = "fused" if headline == "fused" else "engine"
+    modes = ("engine", "launches", "signal", "fused") if full else (hm,)
     mw = 0
-    if share > 1:
+    if share > 1 and "engine" in modes:
         e0 = hq.Engine(ctx, w["n"], w["form"], lay, ring_len=16)
         mw = max(1, e0.info().grid // share)
         e0.close()
-    eng = hq.Engine(ctx, w["n"], w["form"], lay, ring_len=16, max_workgroups=mw)
-    # the same engine with per-step completion flags (what a step worker that applies each step's
-    # commits as soon as they are decided runs): its windows are reported beside the others
-    eng_sig = hq.Engine(ctx, w["n"], w["form"], lay, ring_len=16, signal=True, max_workgroups=mw)
+    eng = eng_sig = None
+    if "engine" in modes:
+        eng = hq.Engine(ctx, w["n"], w["form"], lay, ring_len=16, max_workgroups=mw)
+    if "signal" in modes:
+        # the same engine with per-step completion flags (what a step worker that applies each
+        # step's commits as soon as they are decided runs): its windows are reported beside the
+        # others
+        eng_sig = hq.Engine(ctx, w["n"], w["form"], lay, ring_len=16, signal=True,
+                            max_workgroups=mw)
+    set_args = [batch_args(s[0]) for s in sets]
 
     def arr(i0, k):
-        return hq.commit_batch_array([batch_args(sets[(i0 + i) % nsets][0]) for i in range(k)])
+        return hq.commit_batch_array([set_args[(i0 + i) % nsets] for i in range(k)])
 
     W = max(1, warmup)
-    eng.run(arr(0, W))
-    eng_sig.post(arr(0, W))
-    eng_sig.drain()
-    eng_sig.timing(reset=True)
-    ctx.commit_many_dev(arr(0, min(W, nsets)))
-    ctx.sync()
-    eng.timing(reset=True)
+    if full:
+        eng.run(arr(0, W))
+        eng_sig.post(arr(0, W))
+        eng_sig.drain()
+        eng_sig.timing(reset=True)
+        ctx.commit_many_dev(arr(0, min(W, nsets)))
+        ctx.sync()
+        eng.timing(reset=True)
+    elif hm == "fused":      # as a timed window runs: the HIP-event region around the launches
+        # (at least one pass over every batch, which the other modes' passes give each window
+        # under --full: after 5 warm-up steps alone a 20-step window took 10.1-10.5 us of kernel
+        # time per step against the 9.9 us of a --full run's windows)
+        W = max(W, nsets)
+        ctx.timing(True)
+        for c0, cn in fused_chunks(W):
+            ctx.commit_fused_dev(arr(c0, cn))
+        ctx.timing(False)
+        ctx.sync()
+    else:
+        W = max(W, nsets)
+        eng.run(arr(0, W))
+        eng.timing(reset=True)
     first = W % nsets
     wins = []
     for k in range(windows):
-        a = arr(first + k * steps, steps)
-        a1 = [arr(first + k * steps + i, 1) for i in range(steps)]
-        fa = [arr(first + k * steps + c0, cn) for c0, cn in fused_chunks(steps)]
+        a = arr(first + k * steps, steps) if full else None
+        a1 = [arr(first + k * steps + i, 1) for i in range(steps)] if eng else None
+        fa = ([arr(first + k * steps + c0, cn) for c0, cn in fused_chunks(steps)]
+              if "fused" in modes else None)
         rec = {}
-        for mode in ("engine", "launches", "signal", "fused"):
+        for mode in modes:
             ctx.sync()
             d.sync_device()
             d.barrier()
@@ -691,6 +783,28 @@ def run_engine(w, steps, warmup, d: Dist, windows=3, headline="fused", share=1):
     def med(mode, key):
         return float(np.median([x[mode][key] for x in wins]))
 
+    if dump:
+        last = (first + windows * steps - 1) % nsets
+        dump_outputs(dump, step_outputs(ctx, w, sets[last]), d.rank, d.world)
+    elapsed = med(hm, "elapsed")
+    kernel_s = med(hm, "kernel_s")
+    local = med(hm, "local")
+    achieved_local = per_set / kernel_s / 1e9
+    per_gpu = d.gather([groups_per_step(w) * steps / local, kernel_s * 1e6, achieved_local])
+    achieved_node = d.sum(achieved_local)
+    total_groups = d.sum(float(groups_per_step(w) * steps))
+    res = dict(
+        elapsed=elapsed, launches=steps, avg_kernel_s=kernel_s,
+        decisions=total_groups * decisions_per_group(w), nsets=nsets, first_timed_set=first,
+        bytes_per_launch=per_set, launches_per_step=1, steps=steps,
+        achieved_gbs=achieved_local, achieved_node_gbs=achieved_node, per_gpu=per_gpu,
+        set0=None, gather=None, windows=len(wins), headline_mode=hm,
+    )
+    if not full:
+        if eng:
+            eng.close()
+        ctx.close()
+        return res
     # set 0 once more through the engine, its outputs poisoned first: the full-size parity check
     # of the cpu_baseline leg reads what the engine wrote; the launch path's decisions of the
     # same batch must be identical
@@ -720,22 +834,10 @@ def run_engine(w, steps, warmup, d: Dist, windows=3, headline="fused", share=1):
         set0[0]["out"] = fused_outs
     eng.close()
     eng_sig.close()
-    hm = "fused" if headline == "fused" else "engine"
-    elapsed = med(hm, "elapsed")
-    kernel_s = med(hm, "kernel_s")
-    local = med(hm, "local")
-    achieved_local = per_set / kernel_s / 1e9
-    per_gpu = d.gather([groups_per_step(w) * steps / local, kernel_s * 1e6, achieved_local])
-    achieved_node = d.sum(achieved_local)
-    total_groups = d.sum(float(groups_per_step(w) * steps))
     lk = med("launches", "kernel_s")
     le = med("launches", "elapsed")
-    res = dict(
-        elapsed=elapsed, launches=steps, avg_kernel_s=kernel_s,
-        decisions=total_groups * decisions_per_group(w), nsets=nsets, first_timed_set=first,
-        bytes_per_launch=per_set, launches_per_step=1, steps=steps,
-        achieved_gbs=achieved_local, achieved_node_gbs=achieved_node, per_gpu=per_gpu,
-        set0=set0, gather=None, windows=len(wins), headline_mode=hm,
+    res.update(
+        set0=set0,
         engine={
             "mode": "persistent commit engine (hq_engine), post-as-ready: the window's "
                     f"{steps} steps ({groups_per_step(w)} groups each) posted one hq_engine_post "
@@ -2509,6 +2611,7 @@ def run_rank(args, d, progress):
     """Everything one rank measures: the headline, the extra legs, and (rank 0 at N = 1) the CPU
     baseline. Every rank runs the same legs in the same order (their collectives pair up)."""
     w = WORKLOADS[args.workload]
+    full = args.full
     use_engine = args.mode in ("engine", "fused") and engine_ok(w)
     progress(f"headline {args.workload}: {args.windows if use_engine else 1} x {args.steps} steps"
              f" ({args.mode if use_engine else 'launch per step'}), {args.warmup} warmup")
@@ -2520,9 +2623,14 @@ def run_rank(args, d, progress):
     # engines, so that every engine's grid is resident at once
     per_device = max(1, d.world // max(1, len({x["pci_bus_id"] or x["device"] for x in devices})))
     r = (run_engine(w, args.steps, args.warmup, d, windows=args.windows, headline=args.mode,
-                    share=per_device)
-         if use_engine else run_gpu(w, args.steps, args.warmup, d))
+                    share=per_device, full=full, dump=args.dump_outputs)
+         if use_engine else run_gpu(w, args.steps, args.warmup, d, full=full,
+                                    dump=args.dump_outputs))
     r["world"] = d.world
+    if not full:    # the headline alone: no oracle check, no CPU baseline, no extra legs
+        r.pop("set0", None)
+        r["parity"], r["parity_by_rank"] = None, [None] * d.world
+        return dict(r=r, devices=devices, records=[], cpu=None, forms=[])
     host_threads, _ = cpu_thread_counts()
     progress("full-size parity of every rank's set 0")
     rank_parity(w, r, d, args.no_cpu)
@@ -2647,6 +2755,7 @@ def report(args, d, res, launcher):
         "n_gpus": d.world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": bool(args.full),
         "ms_per_step": r["elapsed"] / args.steps * 1e3,
         "higher_is_better": True,
         "scaling": "weak",
@@ -2657,7 +2766,9 @@ def report(args, d, res, launcher):
                 + (f"; {r['windows']} timed windows of {args.steps} steps, the median window "
                    f"reported (every window in "
                    f"{'fused_window' if r.get('headline_mode') == 'fused' else 'engine'}"
-                   f".window_ms)" if r.get("windows") else ""),
+                   f".window_ms)" if r.get("engine") else
+                   f"; {r['windows']} timed window(s) of {args.steps} steps, the median reported"
+                   if r.get("windows") else ""),
         "config": {
             "workload": args.workload,
             "desc": w["desc"],
@@ -2669,7 +2780,8 @@ def report(args, d, res, launcher):
             else "columns",
             "global_groups_per_step": groups_per_step(w) * d.world,
             **({"headline_mode": r["headline_mode"], "steps_per_window": args.steps,
-                "groups_per_launch": (r["fused_window"]["groups_per_launch"]
+                "groups_per_launch": ([cn * groups_per_step(w)
+                                       for _, cn in fused_chunks(args.steps)]
                                       if r["headline_mode"] == "fused" else
                                       "one resident launch per window")}
                if r.get("headline_mode") else {}),
@@ -2686,7 +2798,8 @@ def report(args, d, res, launcher):
             "kernel_time": ("HIP events around the fused launch(es) of the median window, / "
                             "steps" if r.get("headline_mode") == "fused" else
                             "HIP events around the resident engine launch of the median "
-                            "window (steps posted one by one, then STOP), / steps" if r.get("engine") else
+                            "window (steps posted one by one, then STOP), / steps"
+                            if r.get("headline_mode") == "engine" else
                             "HIP events on the launch stream around the timed launches "
                             "(back to back), / launches"),
             "achieved_scope": f"sum over {d.world} GPU(s) of bytes per launch / kernel time",
@@ -2788,10 +2901,23 @@ def main():
                     help="headline commit steps: the co-resident step workers' batches fused "
                          "into launches of up to 32 (fused), the persistent engine (one resident "
                          "launch per window), or one launch per step; fused and engine apply to "
-                         "uniform tiled term-start / mask workloads, others take launches. All "
-                         "three are timed on the same windows and reported")
-    ap.add_argument("--windows", type=int, default=3,
-                    help="timed windows of --steps steps (engine mode); the median is reported")
+                         "uniform tiled term-start / mask workloads, others take launches. With "
+                         "--full all three are timed on the same windows and reported")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the other ways of running its steps (engine, "
+                         "engine with completion flags, one launch per step) on the same windows, "
+                         "the full-size oracle check, the CPU baseline and the extra legs "
+                         "(--extra). Without it --no-cpu, --no-extra-parity, --extra, "
+                         "--step-groups and --step-steps have nothing to act on")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step (what the caller of the timed "
+                         "path receives: per group the committed index, the changed and fallback "
+                         "bits; confirmed bit and vote outcome for the bitmap workloads) as "
+                         "DIR/<name>.npy, float64 / float32, at most 60 MB in all (a fixed seeded "
+                         "sample of larger outputs)")
+    ap.add_argument("--windows", type=int, default=None,
+                    help="timed windows of --steps steps (fused / engine headline); the median "
+                         "is reported (default: 1, with --full 3)")
     ap.add_argument("--step-groups", type=int, default=1 << 20,
                     help="groups per GPU of the step-worker legs (extras 'step', 'step5')")
     ap.add_argument("--step-steps", type=int, default=50,
@@ -2805,6 +2931,8 @@ def main():
     ap.add_argument("--detail-out", default=os.path.join(ROOT, "gpurun_out", "bench_detail.json"),
                     help="where the full record (every extra leg) is written")
     args = ap.parse_args()
+    if args.windows is None:
+        args.windows = 3 if args.full else 1
     t_start = time.perf_counter()
     world_env = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and world_env == 1:

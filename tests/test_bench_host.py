@@ -95,7 +95,7 @@ def test_thread_dist_collectives(n):
 def _args(**kw):
     a = dict(gpus=2, steps=5, warmup=1, workload=bench.HEADLINE, step_groups=1 << 10,
              step_steps=2, no_cpu=True, no_extra_parity=True, extra="", detail_out=None,
-             mode="fused", windows=3)
+             mode="fused", windows=3, full=True, dump_outputs=None)
     a.update(kw)
     return argparse.Namespace(**a)
 
@@ -194,6 +194,69 @@ def test_host_cores_reports_counts():
     assert visible >= 1 and 1 <= usable <= visible
     allc, counts = bench.cpu_thread_counts()
     assert counts[0] == allc and counts[-1] == 1 and 1 <= allc <= usable
+
+
+def test_plain_run_measures_the_headline_only(monkeypatch, tmp_path, hq):
+    """Without --full a rank runs the headline's own mode and nothing else (no oracle check, no
+    CPU baseline, no extra leg, whatever --extra and --no-cpu say), and the line still carries
+    the headline's figures with ms_per_step = the timed window / --steps."""
+    seen = {}
+
+    def fake_engine(w, steps, warmup, d, **kw):
+        seen.update(kw, steps=steps, warmup=warmup)
+        G = w["G"]
+        return dict(elapsed=2e-4, launches=steps, avg_kernel_s=9.9e-6, decisions=float(G * steps),
+                    nsets=20, first_timed_set=0, bytes_per_launch=58 * G, launches_per_step=1,
+                    steps=steps, achieved_gbs=6000.0, achieved_node_gbs=6000.0,
+                    per_gpu=[[1e11, 9.9, 6000.0]], set0=None, gather=None, windows=1,
+                    headline_mode="fused")
+
+    def never(*a, **kw):
+        raise AssertionError("a plain run measures the headline only")
+    monkeypatch.setattr(bench, "run_engine", fake_engine)
+    for name in ("run_gpu", "cpu_baseline", "full_size_parity", "run_kernel_leg", "run_step_leg",
+                 "run_e2e", "run_size_sweep", "run_concurrent", "run_wire_leg"):
+        monkeypatch.setattr(bench, name, never)
+    monkeypatch.setattr(hq, "device_pci_bus_id", lambda dev: "")
+    args = _args(gpus=1, steps=20, warmup=5, full=False, windows=1, extra=None, no_cpu=False,
+                 no_extra_parity=False, dump_outputs=str(tmp_path / "dump"),
+                 detail_out=str(tmp_path / "detail.json"))
+    d = bench.Dist()
+    res = bench.run_rank(args, d, lambda msg: None)
+    assert seen["full"] is False and seen["dump"] == args.dump_outputs and seen["windows"] == 1
+    assert (seen["steps"], seen["warmup"]) == (20, 5)
+    assert res["records"] == [] and res["cpu"] is None and res["forms"] == []
+    buf = io.StringIO()
+    with redirect_stdout(buf):
+        bench.report(args, d, res, "one process")
+    line = json.loads(buf.getvalue())
+    assert line["full"] is False and line["cpu_baseline"] is None and line["extra"] == {}
+    assert line["ms_per_step"] == pytest.approx(2e-4 / 20 * 1e3)
+    assert line["value"] == pytest.approx(bench.WORKLOADS[bench.HEADLINE]["G"] * 20 / 2e-4)
+    assert (line["unit"], line["dtype"], line["higher_is_better"]) == ("decisions/s", "u64", True)
+    assert "engine" not in line and "fused_window" not in line
+
+
+def test_dump_outputs_files(monkeypatch, tmp_path):
+    """--dump-outputs: packed bits and 2-bit codes come out one value per group, every column
+    as exact floats; above the size limit every array keeps the same seeded sample, run to run."""
+    words = np.array([0b1011 | (1 << 63), 0b100000], np.uint64)
+    assert bench.unpack_bits(words, 70).tolist() == [1, 1, 0, 1] + [0] * 59 + [1] + [0] * 5 + [1]
+    assert bench.unpack_bits(np.array([0b100111], np.uint64), 3, 2).tolist() == [3, 1, 2]
+    big = np.arange(1000, dtype=np.uint64) + np.uint64(1 << 40)
+    arrays = {"committed": big, "changed": (np.arange(1000) % 3 == 0).astype(np.uint8)}
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    got = np.load(tmp_path / "a" / "committed.npy")
+    assert got.dtype == np.float64 and np.array_equal(got.astype(np.uint64), big)
+    chg = np.load(tmp_path / "a" / "changed.npy")
+    assert chg.dtype == np.float32 and np.array_equal(chg, arrays["changed"])
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 6000)      # the two arrays hold 12000 bytes
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    bench.dump_outputs(str(tmp_path / "c"), arrays, rank=1, world=2)
+    s1 = np.load(tmp_path / "b" / "committed.npy")
+    s2 = np.load(tmp_path / "c" / "rank1_committed.npy")
+    assert len(s1) == 500 and np.array_equal(s1, s2) and np.all(np.diff(s1) > 0)
+    assert len(np.load(tmp_path / "b" / "changed.npy")) == 500
 
 
 def test_fused_chunks_cover_the_window():

@@ -17,7 +17,7 @@ for v in default $VARIANTS; do
     *) export HQ_LIB_PATH=tools/lib_$v/libhipquorum.so ;;
   esac
   timeout -k 10 120 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$v -o run -- \
-    python3 bench.py --workload c2tl --extra $LEG --no-cpu --steps 40 --warmup 5 \
+    python3 bench.py --full --workload c2tl --extra $LEG --no-cpu --steps 40 --warmup 5 \
     --detail-out $OUT/$v/detail.json > $OUT/$v.log 2>&1 || exit $?
   echo "== $v"
   grep -h "k_bin\|k_apply\|k_table_ingest" $OUT/$v/run_kernel_stats.csv | \

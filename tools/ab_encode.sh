@@ -11,7 +11,7 @@ for r in $(seq 1 $ROUNDS); do
     if [ $v = default ]; then unset HQ_LIB_PATH; else export HQ_LIB_PATH=tools/lib_$v/libhipquorum.so; fi
     echo "== $v round $r"
     timeout -k 10 120 python3 tools/enc_probe.py || exit $?
-    timeout -k 10 300 python3 bench.py --steps 5 --warmup 2 --extra step5 --no-cpu \
+    timeout -k 10 300 python3 bench.py --full --steps 5 --warmup 2 --extra step5 --no-cpu \
       --detail-out $O/$v$r.json > $O/$v$r.log 2>&1 || exit $?
     python3 - $O/$v$r.json <<'PY'
 import json, sys

@@ -9,7 +9,7 @@ mkdir -p gpurun_out/ab_legs
 for r in $(seq 1 $ROUNDS); do
   for v in default $VARIANTS; do
     if [ $v = default ]; then unset HQ_LIB_PATH; else export HQ_LIB_PATH=tools/lib_$v/libhipquorum.so; fi
-    timeout -k 10 200 python3 bench.py --workload c2tl --extra $LEGS --no-cpu --steps ${STEPS:-200} \
+    timeout -k 10 200 python3 bench.py --full --workload c2tl --extra $LEGS --no-cpu --steps ${STEPS:-200} \
       --warmup 20 --detail-out gpurun_out/ab_legs/$v$r.json > gpurun_out/ab_legs/$v$r.log 2>&1 || exit $?
     python3 - gpurun_out/ab_legs/$v$r.log $v <<'PY'
 import json, sys

@@ -10,7 +10,7 @@ mkdir -p gpurun_out/ab
 for r in $(seq 1 $ROUNDS); do
   for v in A B; do
     if [ $v = A ]; then unset HQ_LIB_PATH; else export HQ_LIB_PATH=$B; fi
-    timeout -k 10 120 python3 bench.py --workload $HEAD --extra=$LEGS --no-cpu --steps 400 \
+    timeout -k 10 120 python3 bench.py --full --workload $HEAD --extra=$LEGS --no-cpu --steps 400 \
       --warmup 20 ${EXTRA_ARGS:-} > gpurun_out/ab/$v$r.log 2>&1 || exit $?
     python3 - gpurun_out/ab/$v$r.log $v <<'PY'
 import json, sys

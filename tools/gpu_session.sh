@@ -12,14 +12,15 @@
 # (replaces the round-2 gpu_r02.sh and the round-3 one-off g1.sh ... g17.sh, which git history
 # keeps as they were run)
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
-mkdir -p gpurun_out
+O=${OUT:-bench_out}
+mkdir -p $O
 export TMPDIR=/tmp
 step() {  # step <name> <timeout> <cmd...>
   local name=$1 t=$2; shift 2
   echo "== $name: $*"
-  timeout -k 10 "$t" "$@" > "gpurun_out/$name.log" 2>&1
+  timeout -k 10 "$t" "$@" > "$O/$name.log" 2>&1
   local rc=$?
-  echo "== $name rc=$rc"; tail -n 3 "gpurun_out/$name.log" | cut -c1-400
+  echo "== $name rc=$rc"; tail -n 3 "$O/$name.log" | cut -c1-400
   return $rc
 }
 fatal() { [ "$1" -ne 0 ] && [ "$1" -ne 1 ]; }
@@ -31,14 +32,14 @@ if [ "${SKIP_TESTS:-0}" != 1 ]; then
   rc=$?; if fatal $rc; then exit $rc; fi
 fi
 if [ "${SKIP_BENCH:-0}" != 1 ]; then
-  step bench 600 python -u bench.py ${BENCH_ARGS:-}
+  step bench 600 python -u bench.py --full ${BENCH_ARGS:-}
   rc=$?; if fatal $rc; then exit $rc; fi
-  tail -n 1 gpurun_out/bench.log | wc -c
+  tail -n 1 $O/bench.log | wc -c
 fi
 # launcher-free multi-GPU path, rehearsed with two host threads (two contexts on one GPU)
 if [ "${REHEARSE:-1}" = 1 ]; then
-  step bench_n2_threads 300 python -u bench.py --gpus 2 --steps 20 --warmup 5 --no-cpu \
-    --extra c5v5tl,c4p,cqp --detail-out gpurun_out/bench_n2_detail.json
+  step bench_n2_threads 300 python -u bench.py --full --gpus 2 --steps 20 --warmup 5 --no-cpu \
+    --extra c5v5tl,c4p,cqp --detail-out $O/bench_n2_detail.json
   rc=$?; if fatal $rc; then exit $rc; fi
 fi
 # the driver's multi-GPU launch (torchrun, one rank per GPU), rehearsed with two ranks sharing
@@ -46,13 +47,13 @@ fi
 # eight contexts on the one GPU
 if [ "${REHEARSE_TORCHRUN:-0}" = 1 ]; then
   step bench_torchrun_n2 300 python -u -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-    --master-addr 127.0.0.1 --master-port 29531 bench.py --gpus 2 --steps 20 --warmup 5 --no-cpu \
-    --extra c5v5tl --detail-out gpurun_out/bench_torchrun_n2_detail.json
+    --master-addr 127.0.0.1 --master-port 29531 bench.py --full --gpus 2 --steps 20 --warmup 5 --no-cpu \
+    --extra c5v5tl --detail-out $O/bench_torchrun_n2_detail.json
   rc=$?; if fatal $rc; then exit $rc; fi
 fi
 if [ "${REHEARSE8:-0}" = 1 ]; then
-  step bench_c5tl_n8_threads 400 python -u bench.py --gpus 8 --workload c5tl --steps 20 \
-    --warmup 5 --no-cpu --extra= --detail-out gpurun_out/bench_c5tl_n8_detail.json
+  step bench_c5tl_n8_threads 400 python -u bench.py --full --gpus 8 --workload c5tl --steps 20 \
+    --warmup 5 --no-cpu --extra= --detail-out $O/bench_c5tl_n8_detail.json
   rc=$?; if fatal $rc; then exit $rc; fi
 fi
 for A in ${AB:-}; do

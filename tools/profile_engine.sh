@@ -7,7 +7,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 W=${1:-c3mtl}
 OUT=gpurun_out/prof_${W}-engine
-ARGS="--workload $W --extra= --steps 20 --warmup 5 --no-cpu"
+ARGS="--full --workload $W --extra= --steps 20 --warmup 5 --no-cpu"
 mkdir -p $OUT
 set -o pipefail
 echo "== kernel trace ($W, engine)"
