@@ -48,14 +48,16 @@ KERNEL_FUSED = {"c3mtl": "k_commit_fused<2, 1024, 2>"}
 # the default line's headline mode "engine" (bench.py run_engine): the persistent engine's launch
 # per timed window of --steps steps; its dispatches are the warm-up (warmup steps), the timed
 # windows (steps each, in order) and the parity launch (1 step). Per step: a window dispatch's
-# duration or counter over its steps.
-KERNEL_ENGINE = {"c3mtl-engine": ("c3mtl", "k_commit_engine<5, 2, 1, false, 1024, false, false>")}
+# duration or counter over its steps. Two spellings of the kernel: traces up to profiles/r06* carry
+# a seventh template argument (the balanced claim mode, false in every profiled run).
+KERNEL_ENGINE = {"c3mtl-engine": ("c3mtl", ("k_commit_engine<5, 2, 1, false, 1024, false>",
+                                            "k_commit_engine<5, 2, 1, false, 1024, false, false>"))}
 ENGINE_STEPS, ENGINE_WARMUP, ENGINE_WINDOWS = 20, 5, 3
 
 
-def engine_windows(path, kernel, value_key):
+def engine_windows(path, kernels, value_key):
     """per-step values of the timed-window dispatches (2nd .. windows + 1st of the kernel's)."""
-    rows = [r for r in csv.DictReader(open(path)) if kernel in r["Kernel_Name"]]
+    rows = [r for r in csv.DictReader(open(path)) if any(k in r["Kernel_Name"] for k in kernels)]
     rows.sort(key=lambda r: int(r.get("Dispatch_Id") or r.get("Correlation_Id") or 0))
     wins = rows[1:1 + ENGINE_WINDOWS]
     return [value_key(r) / ENGINE_STEPS for r in wins], len(rows)
@@ -98,7 +100,7 @@ def main():
                                        lambda r: float(r["Counter_Value"]))
             f_med, w_med = statistics.median(fetch), statistics.median(write)
             traffic[w] = {
-                "kernel": k, "mode": "engine",
+                "kernel": k[0], "mode": "engine",
                 "rocprof_window_ns_per_step": ns, "rocprof_avg_ns": statistics.median(ns),
                 "rocprof_calls": nd, "steps_per_window": ENGINE_STEPS,
                 "fetch_size_kb_median": f_med, "write_size_kb_median": w_med,
