@@ -84,6 +84,10 @@ struct hq_dstep_in {
     const uint32_t *sizes = nullptr;   // per group: events | bytes << 16
     uint64_t n_events = 0, n_bytes = 0;
     const uint16_t *sizes16 = nullptr; // or per group: bytes (the engine counts the events)
+    // rows already on the device (the wire's device mode, hq_wire_dev.hip): groups (NULL: handles
+    // 0 .. n - 1), offsets and events are device pointers, n_events the rows' count; nothing of
+    // them is read on the host, one chunk, device-to-device copies on the compute stream
+    bool on_device = false;
 };
 
 // commit_column: bit 1 a step may return its commits as a column (HQ_WORKER_COMMIT_COLUMN), bit 2
@@ -112,3 +116,13 @@ constexpr uint32_t kDStepMaxJobs = 64;
 // launches when they allow it; kJobsNotFused (nothing done) when they do not
 constexpr int kJobsNotFused = 1 << 30;
 int hq_worker_step_jobs_fused(hq_step_job *jobs, uint32_t count);
+
+// hq_worker.cpp, for the wire's device mode (hq_wire_dev.hip): a device worker's context (NULL:
+// not a device worker), the cluster ids of handles [h0, h0 + n), and hq_worker_step over rows that
+// are already on the device (hq_dstep_in::on_device; queued on the context's stream behind
+// whatever produced them)
+hq_ctx *hq_worker_device_ctx(hq_worker *w);
+int hq_worker_cluster_ids(hq_worker *w, uint64_t h0, uint64_t n, uint64_t *out);
+int hq_worker_step_device_rows(hq_worker *w, uint64_t n, const uint32_t *groups,
+                               const uint64_t *offsets, const hq_event *events, uint64_t n_events,
+                               hq_step_output *out);

@@ -2050,14 +2050,16 @@ int prepare(Run &r, hipStream_t s, bool jobs = false) {
     r.sized = r.stream && (in->sizes != nullptr || in->sizes16 != nullptr);   // scanned here
     const bool stream = r.stream, sized = r.sized;
     const bool s16 = sized && in->sizes16 != nullptr;   // 2-byte words: bytes only
-    const uint64_t ne = r.ne = sized ? in->n_events : in->offsets[n];
+    const bool on_dev = in->on_device && !stream;   // rows on the device: nothing read here
+    const uint64_t ne = r.ne = sized || on_dev ? in->n_events : in->offsets[n];
     const uint64_t nb = r.nb = !stream ? 0 : sized ? in->n_bytes : in->boffsets[n];
     if (sized && (ne >> 32 || nb >> 32))     // the scanned prefixes pack both totals in 64 bits
         return hq::fail(ctx, HQ_E_INVAL, "hq_dstep: a sized step holds < 2^32 events and bytes");
     r.t0 = now_ns();
     int rc = hq::check_hip(ctx, hipSetDevice(ctx->device), "hipSetDevice");
     // chunks of groups (at least 64 Ki each): chunk c's input copy overlaps pass A of chunk c - 1
-    while (r.chunks * 2 <= kMaxChunks && n >= (uint64_t)r.chunks * 2 * kChunkGroups) r.chunks *= 2;
+    while (!on_dev && r.chunks * 2 <= kMaxChunks && n >= (uint64_t)r.chunks * 2 * kChunkGroups)
+        r.chunks *= 2;
     // the step's input in one device region: handles, offsets, [boffsets,] events or bytes, each
     // at the offsets it has on the host; a sized stream: handles, sizes (+ a zero), their scan,
     // bytes
@@ -2149,7 +2151,7 @@ int prepare(Run &r, hipStream_t s, bool jobs = false) {
     k.i_end = n;
     k.own_lo = 0;
     k.own_hi = UINT64_MAX;
-    k.handles = sized && !in->groups ? nullptr : reinterpret_cast<const uint32_t *>(din);
+    k.handles = (sized || on_dev) && !in->groups ? nullptr : reinterpret_cast<const uint32_t *>(din);
     k.offsets = reinterpret_cast<const uint64_t *>(din + r.o_off);
     if (sized) {
         k.prefix = prefix;
@@ -2539,8 +2541,24 @@ int hq_dstep_run(hq_dstep *d, const hq_dstep_in *in, hq_dstep_out *out) {
         }
         rc = r.rc;
     }
+    // rows on the device: the three arrays into the input region as they are (one chunk)
+    const bool on_dev = in->on_device && !stream;
+    if (on_dev) {
+        auto d2d = [&](size_t off, const void *src, size_t bytes) {
+            if (!rc && bytes)
+                rc = hq::check_hip(ctx, hipMemcpyAsync(din + off, src, bytes,
+                                                       hipMemcpyDeviceToDevice, ctx->stream),
+                                   "hq_dstep D2D");
+        };
+        if (in->groups) d2d(0, in->groups, n * 4);
+        d2d(r.o_off, in->offsets, (n + 1) * 8);
+        d2d(r.o_ev, in->events, ne * sizeof(hq_event));
+        r.rc = rc;
+        launch_pass(r, false, 0, n);
+        rc = r.rc;
+    }
     // inputs chunk by chunk, pass A of each chunk once it has landed
-    for (int c = 0; c < chunks && !rc && !sized; ++c) {
+    for (int c = 0; c < chunks && !rc && !sized && !on_dev; ++c) {
         const uint64_t i0 = bound[c], i1 = bound[c + 1];
         h2d(i0 * 4, in->groups + i0, (i1 - i0) * 4);
         h2d(r.o_off + i0 * 8, in->offsets + i0, (i1 - i0 + 1) * 8);

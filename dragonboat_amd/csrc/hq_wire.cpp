@@ -20,6 +20,7 @@
 
 #include "../../include/hipquorum.h"
 #include "hq_stream.h"
+#include "hq_wire_dev.h"
 
 namespace {
 
@@ -385,6 +386,14 @@ struct hq_wire {
     std::vector<uint8_t> bytes;
     std::vector<uint32_t> cnt, perm, pos;   // hq_wire_step_sized's counting sort
     std::vector<uint32_t> kcnt;        // attached: the records queued per handle (at h + 1)
+    // the device mode (hq_wire_attach_device): batches are framed here and queued there; recs
+    // holds the local events only
+    hq_wire_dev *dev = nullptr;
+    std::vector<hq_wire_span> spans;   // one batch's spans
+    uint32_t batch_calls = 0;          // hq_wire_add_batch calls since the last reset
+    const uint32_t *rejected = nullptr;   // the last device step's malformed batches
+    uint64_t n_rejected = 0;
+    uint64_t dev_queued = 0;           // messages queued on the device side
 
     void count_key(uint32_t k) {
         if ((size_t)k + 2 > kcnt.size()) kcnt.resize(std::max<size_t>((size_t)k + 2, 2 * kcnt.size()), 0);
@@ -537,13 +546,44 @@ int hq_wire_open(uint64_t deployment_id, hq_wire **out) {
     return HQ_OK;
 }
 
-void hq_wire_close(hq_wire *w) { delete w; }
+void hq_wire_close(hq_wire *w) {
+    if (w && w->dev) hq_wire_dev_close(w->dev);
+    delete w;
+}
 
 const char *hq_wire_last_error(const hq_wire *w) { return w ? w->err.c_str() : ""; }
 
 int hq_wire_attach(hq_wire *w, hq_worker *worker) {
     if (!w) return HQ_E_INVAL;
-    if (!w->recs.empty()) return w->fail(HQ_E_STATE, "hq_wire_attach: events queued (reset first)");
+    if (!w->recs.empty() || w->dev_queued)
+        return w->fail(HQ_E_STATE, "hq_wire_attach: events queued (reset first)");
+    if (w->dev) {                      // back from the device mode
+        hq_wire_dev_close(w->dev);
+        w->dev = nullptr;
+        w->rejected = nullptr;
+        w->n_rejected = 0;
+    }
+    w->worker = worker;
+    w->handle_of = ClusterIndex();
+    w->kcnt.clear();
+    return HQ_OK;
+}
+
+int hq_wire_attach_device(hq_wire *w, hq_worker *worker) {
+    if (!w) return HQ_E_INVAL;
+    if (!worker) return w->fail(HQ_E_INVAL, "hq_wire_attach_device: NULL worker");
+    if (!w->recs.empty() || w->dev_queued)
+        return w->fail(HQ_E_STATE, "hq_wire_attach_device: events queued (reset first)");
+    hq_wire_dev *dev = nullptr;
+    const int rc = hq_wire_dev_open(worker, &dev);
+    if (rc)
+        return w->fail(rc, rc == HQ_E_INVAL ? "hq_wire_attach_device: not a device worker "
+                                              "(HQ_WORKER_ON_DEVICE)"
+                                            : "hq_wire_attach_device: device buffers");
+    if (w->dev) hq_wire_dev_close(w->dev);
+    w->dev = dev;
+    w->rejected = nullptr;
+    w->n_rejected = 0;
     w->worker = worker;
     w->handle_of = ClusterIndex();
     w->kcnt.clear();
@@ -552,6 +592,11 @@ int hq_wire_attach(hq_wire *w, hq_worker *worker) {
 
 int hq_wire_reset(hq_wire *w) {
     if (!w) return HQ_E_INVAL;
+    if (w->dev) hq_wire_dev_reset(w->dev);
+    w->batch_calls = 0;
+    w->dev_queued = 0;
+    w->rejected = nullptr;
+    w->n_rejected = 0;
     w->recs.clear();
     std::fill(w->kcnt.begin(), w->kcnt.end(), 0u);
     w->clusters.clear();
@@ -606,9 +651,41 @@ int hq_wire_add_locals(hq_wire *w, uint64_t n, const uint64_t *cluster_ids, cons
     return HQ_OK;
 }
 
+// The device mode: the batch framed (no message looked into), its own fields checked as below, its
+// spans queued for hq_wire_step_device
+static int add_batch_device(hq_wire *w, const uint8_t *bytes, size_t len) {
+    const uint32_t index = w->batch_calls++;
+    if (w->spans.empty()) w->spans.resize(1024);
+    hq_wire_batch_info bi;
+    uint64_t ns = 0;
+    int rc = hq_wire_frame_batch(bytes, len, 0, w->spans.data(), w->spans.size(), &ns, &bi);
+    if (rc == HQ_E_STATE) {
+        w->spans.resize(ns);
+        rc = hq_wire_frame_batch(bytes, len, 0, w->spans.data(), w->spans.size(), &ns, &bi);
+    }
+    if (rc) return w->fail(HQ_E_INVAL, "hq_wire_add_batch: malformed MessageBatch");
+    w->stats.batches++;
+    w->stats.bytes += len;
+    if (bi.deployment_id != w->deployment_id || bi.bin_ver != HQ_RPC_BIN_VERSION) {
+        w->stats.dropped_batches++;
+        w->stats.dropped_messages += bi.n_messages;
+        return HQ_OK;
+    }
+    if (bi.n_messages == 0) return HQ_OK;
+    rc = hq_wire_dev_add_batch(w->dev, bytes, len, w->spans.data(), ns, bi.n_messages, index);
+    if (rc) {
+        w->stats.batches--;
+        w->stats.bytes -= len;
+        return w->fail(rc, hq_wire_dev_error(w->dev));
+    }
+    w->dev_queued += bi.n_messages;
+    return HQ_OK;
+}
+
 int hq_wire_add_batch(hq_wire *w, const uint8_t *bytes, size_t len) {
     if (!w) return HQ_E_INVAL;
     if (!bytes && len) return w->fail(HQ_E_INVAL, "hq_wire_add_batch: NULL bytes");
+    if (w->dev) return add_batch_device(w, bytes, len);
     // one pass: every message straight into a record (Message.MarshalTo's field order on the fast
     // path, any order on the general one) with its cluster id aside; the batch's own fields
     // (they follow the messages in the marshalled order) then decide whether the records stay
@@ -771,6 +848,7 @@ int hq_wire_step_sized(hq_wire *w, uint8_t *bytes, uint64_t cap, uint16_t *sizes
                        hq_step_stream *out, hq_wire_stats *stats) {
     if (!w || !out || (cap && !bytes)) return HQ_E_INVAL;
     if (!w->worker) return w->fail(HQ_E_STATE, "hq_wire_step_sized: no worker attached");
+    if (w->dev) return w->fail(HQ_E_STATE, "hq_wire_step_sized: device mode (hq_wire_step_device)");
     uint64_t n = 0;
     if (hq_worker_group_count(w->worker, &n) != HQ_OK) return HQ_E_INVAL;
     if (n > n_cap || (n && !sizes16))
@@ -821,6 +899,36 @@ int hq_wire_step_sized(hq_wire *w, uint8_t *bytes, uint64_t cap, uint16_t *sizes
     out->n_events = events;
     out->n_bytes = (uint64_t)(p - bytes);
     if (stats) *stats = w->stats;
+    return HQ_OK;
+}
+
+int hq_wire_step_device(hq_wire *w, hq_step_output *out, hq_wire_stats *stats) {
+    if (!w || !out) return HQ_E_INVAL;
+    if (!w->dev) return w->fail(HQ_E_STATE, "hq_wire_step_device: no device worker attached");
+    uint64_t c[4], rejected_bytes = 0;
+    const int rc = hq_wire_dev_step(w->dev, static_cast<const hqs::WireEvent *>(w->recs.data()),
+                                    w->recs.size(), out, c, &w->rejected, &w->n_rejected,
+                                    &rejected_bytes);
+    if (rc) return w->fail(rc, hq_wire_dev_error(w->dev));
+    if (stats) {
+        // the kernels' counters beside the host's; a batch dropped for a malformed message is
+        // counted nowhere (as one hq_wire_add_batch rejects)
+        *stats = w->stats;
+        stats->messages += c[0];
+        stats->entries += c[1];
+        stats->snapshot_received += c[2];
+        stats->dropped_no_cluster += c[3];
+        stats->batches -= w->n_rejected;
+        stats->bytes -= rejected_bytes;
+    }
+    return HQ_OK;
+}
+
+int hq_wire_device_rejected(hq_wire *w, const uint32_t **batches, uint64_t *n) {
+    if (!w || !batches || !n) return HQ_E_INVAL;
+    if (!w->dev) return w->fail(HQ_E_STATE, "hq_wire_device_rejected: no device worker attached");
+    *batches = w->rejected;
+    *n = w->n_rejected;
     return HQ_OK;
 }
 

@@ -1,0 +1,716 @@
+// hq_wire_dev.hip — raftpb.Message decode on the device (include/hipquorum.h "wire decode on the
+// device"): the spans hq_wire_frame_batch (hq_wire_frame.cpp) cut out of MessageBatch bytes,
+// decoded into hq_wire_message records, one wave per span and one lane per message.
+//
+// The decoder is the device twin of hq_wire.cpp's decode_message and keeps its treatment of odd
+// but accepted input (any field order, a repeated scalar takes its last value, the tag's field
+// number truncated to 32 bits, unknown fields skipped by wire type). The bytes come from the
+// network: every loop consumes at least one byte of a message per iteration, a varint reads at
+// most 10 bytes, and no byte outside a span is read. The kernel waits on nothing but its own
+// workgroup's two barriers.
+//
+// The device mode of hq_wire (hq_wire_attach_device) follows in the same file: the decoded records
+// keyed by the worker's handle through a device hash table, sorted with the step's local events by
+// (handle, category), turned into rows and per-handle offsets, and handed to the device step
+// (hq_worker_step_device_rows) without returning to the host.
+#include <hipcub/hipcub.hpp>
+
+#include <algorithm>
+#include <cstring>
+#include <new>
+
+#include "hq_dstep.h"
+#include "hq_internal.h"
+#include "hq_wire_dev.h"
+
+namespace {
+
+constexpr uint32_t kSnapshotReceived = 22;   // raft.proto MessageType
+
+constexpr uint32_t kThreads = 256, kWaves = kThreads / 64;   // a wave per span
+
+// A wave's share of LDS: its span's bytes behind the low 4 bits of the span's address (so that a
+// 16-byte word of memory is a 16-byte word of the stage), then where the hop found each message.
+struct WaveStage {
+    uint4 bytes[(HQ_WIRE_SPAN_BYTES + 16) / 16];
+    uint32_t pos[HQ_WIRE_SPAN_MESSAGES];      // a message's body, from the span's first byte
+    uint32_t len[HQ_WIRE_SPAN_MESSAGES];
+    uint32_t framed;                          // the headers are where the span says
+    uint32_t pad[3];
+};
+
+// p < end on entry is not required; I is the position type (32 bits in LDS, 64 in memory)
+template <class I>
+__host__ __device__ __forceinline__ bool varint(const uint8_t *b, I &p, I end, uint64_t &v) {
+    v = 0;
+#pragma unroll 1
+    for (int shift = 0; shift < 64; shift += 7) {
+        if (p >= end) return false;               // unexpected end of data in a varint
+        const uint8_t x = b[p++];
+        v |= (uint64_t)(x & 0x7F) << shift;
+        if (x < 0x80) return true;
+    }
+    return false;                                 // varint overflows 64 bits
+}
+
+// the `requests` header at p: its body's position and length; false when it is not one, or runs
+// past end
+template <class I>
+__host__ __device__ __forceinline__ bool header(const uint8_t *b, I &p, I end, uint64_t &n) {
+    uint64_t tag;
+    if (!varint(b, p, end, tag)) return false;
+    if ((uint32_t)(tag >> 3) != 1 || (uint32_t)(tag & 7) != 2) return false;
+    if (!varint(b, p, end, n)) return false;
+    return (uint64_t)(end - p) >= n;
+}
+
+// decode_message (hq_wire.cpp:84-141) over b[0 .. end); false: rejected
+template <class I>
+__host__ __device__ bool decode_message(const uint8_t *b, I end, hq_wire_message &m) {
+    m = hq_wire_message{};
+    m.ev.kind = HQ_EV_MESSAGE;
+    I p = 0;
+    while (p < end) {
+        uint64_t tag;
+        if (!varint(b, p, end, tag)) return false;
+        const uint32_t field = (uint32_t)(tag >> 3), wt = (uint32_t)(tag & 7);
+        if (field == 0) return false;
+        uint64_t v = 0;
+        if (field <= 10 || field == 13) {             // the varint fields
+            if (wt != 0) return false;
+            if (!varint(b, p, end, v)) return false;
+        }
+        switch (field) {
+        case 1: m.ev.type = (uint32_t)v; break;
+        case 2: m.to = v; break;
+        case 3: m.ev.from = v; break;
+        case 4: m.cluster_id = v; break;
+        case 5: m.ev.term = v; break;
+        case 6: m.log_term = v; break;
+        case 7: m.ev.log_index = v; break;
+        case 8: m.commit = v; break;
+        case 9: m.ev.reject = v != 0; break;
+        case 10: m.ev.hint = v; break;
+        case 13: m.ev.hint_high = v; break;
+        case 11:                                   // entries: counted and skipped
+        case 12: {                                 // the snapshot: noted and skipped
+            if (wt != 2) return false;
+            uint64_t n;
+            if (!varint(b, p, end, n)) return false;
+            if ((uint64_t)(end - p) < n) return false;
+            p += (I)n;
+            if (field == 11) m.n_entries++;
+            else m.has_snapshot = 1;
+            break;
+        }
+        default: {                                 // unknown: skipped by wire type
+            uint64_t n = 0;
+            switch (wt) {
+            case 0:
+                if (!varint(b, p, end, n)) return false;
+                n = 0;
+                break;
+            case 1: n = 8; break;
+            case 2:
+                if (!varint(b, p, end, n)) return false;
+                break;
+            case 5: n = 4; break;
+            default: return false;                 // groups are not part of raft.proto
+            }
+            if ((uint64_t)(end - p) < n) return false;
+            p += (I)n;
+        }
+        }
+    }
+    return true;
+}
+
+// the decode kernel's arguments; REC (the device mode): the records go out as the wire's 56-byte
+// events with their batch in `key` and their entry count in `pad2`, the cluster ids aside, and a
+// rejected message flags its batch
+struct DecodeK {
+    const uint8_t *bytes;
+    uint64_t len;
+    const hq_wire_span *spans;
+    uint64_t n_spans;
+    hq_wire_message *out;
+    uint8_t *status;
+    uint64_t n_messages;
+    const uint32_t *span_batch;
+    uint32_t *bad;
+    hqs::WireEvent *recs;
+    uint64_t *cids;
+};
+
+template <bool REC>
+__global__ void __launch_bounds__(kThreads) k_wire_decode(const DecodeK a) {
+    __shared__ WaveStage stage[kWaves];
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const uint64_t s = (uint64_t)blockIdx.x * kWaves + wave;
+    WaveStage &st = stage[wave];
+
+    hq_wire_span sp{};
+    if (s < a.n_spans) sp = a.spans[s];
+    const bool large = (sp.flags & HQ_WIRE_SPAN_LARGE) != 0;
+    // a span this kernel can take: within the buffer, and within a wave's stage unless large
+    const bool valid = sp.count >= 1 && sp.count <= HQ_WIRE_SPAN_MESSAGES && sp.offset <= a.len &&
+                       sp.len <= a.len - sp.offset &&
+                       (large ? sp.count == 1 : sp.len <= HQ_WIRE_SPAN_BYTES);
+    const uint32_t count = sp.count <= HQ_WIRE_SPAN_MESSAGES ? sp.count : HQ_WIRE_SPAN_MESSAGES;
+    const uint8_t *const g = a.bytes + sp.offset;
+    const uint32_t L = (uint32_t)sp.len;                      // (staged spans: <= 4096)
+    const uint32_t sh = (uint32_t)(reinterpret_cast<uintptr_t>(g) & 15u);
+    uint8_t *const sb = reinterpret_cast<uint8_t *>(st.bytes);
+
+    // stage: whole 16-byte words of memory that lie inside the span as such, the span's ragged
+    // first and last word byte by byte (nothing outside the span is read)
+    if (valid && !large) {
+        const uint4 *const g16 = reinterpret_cast<const uint4 *>(g - sh);
+        const uint32_t words = (sh + L + 15) / 16;
+        for (uint32_t c = lane; c < words; c += 64) {
+            const uint32_t b0 = c * 16;
+            if (b0 >= sh && b0 + 16 <= sh + L) {
+                st.bytes[c] = g16[c];
+            } else {
+                for (uint32_t j = 0; j < 16; ++j)
+                    if (b0 + j >= sh && b0 + j < sh + L) sb[b0 + j] = g[b0 + j - sh];
+            }
+        }
+    }
+    __syncthreads();
+
+    // hop: one lane finds the span's headers
+    if (valid && !large && lane == 0) {
+        const uint8_t *const b = sb + sh;
+        uint32_t p = 0, k = 0;
+        for (; k < count; ++k) {
+            uint64_t n;
+            if (!header<uint32_t>(b, p, L, n)) break;
+            st.pos[k] = p;
+            st.len[k] = (uint32_t)n;
+            p += (uint32_t)n;
+        }
+        st.framed = k == count && p == L;
+    }
+    __syncthreads();
+
+    if (s >= a.n_spans || lane >= count) return;
+    const uint64_t i = (uint64_t)sp.first + lane;
+    if (i >= a.n_messages) return;
+    bool ok = false;
+    hq_wire_message m;
+    if (valid && !large) {
+        if (st.framed) ok = decode_message<uint32_t>(sb + sh + st.pos[lane], st.len[lane], m);
+    } else if (valid) {                               // one message, one lane, from memory
+        uint64_t p = 0, n;
+        if (header<uint64_t>(g, p, sp.len, n) && p + n == sp.len)
+            ok = decode_message<uint64_t>(g + p, n, m);
+    }
+    if (REC) {
+        const uint32_t batch = a.span_batch[s];
+        hqs::WireEvent r{};
+        r.key = batch;
+        r.cat = 1;
+        r.kind = HQ_EV_MESSAGE;
+        if (ok) {
+            r.reject = m.ev.reject != 0;
+            r.type = m.ev.type;
+            r.pad2 = m.n_entries;
+            r.from = m.ev.from;
+            r.term = m.ev.term;
+            r.log_index = m.ev.log_index;
+            r.hint = m.ev.hint;
+            r.hint_high = m.ev.hint_high;
+            a.cids[i] = m.cluster_id;
+        } else {
+            a.bad[batch] = 1;                         // the whole batch goes (k_wire_keys)
+        }
+        a.recs[i] = r;
+    } else {
+        if (ok) a.out[i] = m;
+        a.status[i] = ok ? 0 : 1;
+    }
+}
+
+// ---- the device mode: keys, sort, rows ----
+
+struct Slot {                                         // the handle table: hq_wire.cpp ClusterIndex's
+    uint64_t key;
+    uint32_t val, pad;
+};
+constexpr uint64_t kEmptyKey = ~0ull;                 // the one key the table cannot hold
+
+__host__ __device__ inline uint64_t hash_id(uint64_t x) {
+    x ^= x >> 33;
+    x *= 0xff51afd7ed558ccdull;
+    return x ^ (x >> 33);
+}
+
+struct KeysK {
+    const hqs::WireEvent *recs;
+    const uint64_t *cids;
+    const uint32_t *bad;
+    uint64_t n_msgs, n;                               // records: the messages, then the locals
+    const Slot *slots;
+    uint64_t n_slots;                                 // a power of two
+    uint32_t has_empty, empty_val;
+    uint32_t sentinel;                                // 4 * groups: sorts behind every handle
+    uint32_t *keys, *vals;
+    unsigned long long *counters;                     // messages, entries, snapshot_received,
+};                                                    // dropped_no_cluster
+
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
+    for (int d = 32; d; d >>= 1) v += __shfl_down(v, d, 64);
+    return v;
+}
+
+// every record's sort key, handle * 4 + category, or the sentinel for a record that is dropped: a
+// message of a batch with a malformed message, a SnapshotReceived, a cluster the worker does not
+// run. The counters are the host path's (hq_wire_add_batch), for the batches that stay.
+__global__ void __launch_bounds__(256) k_wire_keys(const KeysK a) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    unsigned long long c[4] = {0, 0, 0, 0};
+    if (i < a.n) {
+        const hqs::WireEvent r = a.recs[i];
+        uint32_t key = a.sentinel;
+        if (i >= a.n_msgs) {                          // a local event: its handle resolved already
+            key = r.key * 4 + r.cat;
+        } else if (!a.bad[r.key]) {
+            c[0] = 1;
+            c[1] = r.pad2;
+            if (r.type == kSnapshotReceived) {
+                c[2] = 1;
+            } else {
+                const uint64_t id = a.cids[i];
+                bool found = false;
+                uint32_t h = 0;
+                if (id == kEmptyKey) {
+                    found = a.has_empty != 0;
+                    h = a.empty_val;
+                } else {
+                    const uint64_t mask = a.n_slots - 1;
+                    uint64_t s = hash_id(id) & mask;
+                    for (uint64_t probe = 0; probe < a.n_slots; ++probe, s = (s + 1) & mask) {
+                        const uint64_t k = a.slots[s].key;
+                        if (k == id) {
+                            found = true;
+                            h = a.slots[s].val;
+                            break;
+                        }
+                        if (k == kEmptyKey) break;
+                    }
+                }
+                if (found) key = h * 4 + 1;
+                else c[3] = 1;
+            }
+        }
+        a.keys[i] = key;
+        a.vals[i] = (uint32_t)i;
+    }
+    for (int k = 0; k < 4; ++k) {
+        const unsigned long long v = wave_sum(c[k]);
+        if ((threadIdx.x & 63) == 0 && v) atomicAdd(&a.counters[k], v);
+    }
+}
+
+// offsets[h] = the first sorted record whose key is at least 4 h, h = 0 .. n_groups (the last: the
+// records that stay)
+__global__ void __launch_bounds__(256) k_wire_offsets(const uint32_t *keys, uint64_t n,
+                                                      uint64_t n_groups, uint64_t *offsets) {
+    const uint64_t h = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (h > n_groups) return;
+    const uint64_t want = h * 4;
+    uint64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (keys[mid] < want) lo = mid + 1;
+        else hi = mid;
+    }
+    offsets[h] = lo;
+}
+
+// the sorted records that stay, as the step's rows
+__global__ void __launch_bounds__(256) k_wire_rows(const hqs::WireEvent *recs, const uint32_t *vals,
+                                                   const uint64_t *n_rows, hq_event *events) {
+    const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= *n_rows) return;
+    const hqs::WireEvent r = recs[vals[j]];
+    hq_event e{};
+    e.kind = r.kind;
+    e.type = r.type;
+    e.from = r.from;
+    e.term = r.term;
+    e.log_index = r.log_index;
+    e.hint = r.hint;
+    e.hint_high = r.hint_high;
+    e.reject = r.reject;
+    events[j] = e;
+}
+
+struct DevBuf {
+    void *p = nullptr;
+    size_t cap = 0;
+};
+
+struct StageBlock {                                   // pinned staging: never moved once allocated
+    uint8_t *host = nullptr, *dev = nullptr;
+    size_t cap = 0, fill = 0;
+};
+
+}  // namespace
+
+extern "C" int hq_wire_decode_dev(hq_ctx *ctx, const uint8_t *bytes, uint64_t len,
+                                  const hq_wire_span *spans, uint64_t n_spans, hq_wire_message *out,
+                                  uint8_t *status, uint64_t n_messages) {
+    if (!ctx) return HQ_E_INVAL;
+    if (n_spans == 0 || n_messages == 0) return HQ_OK;
+    if (!spans || !out || !status || (!bytes && len))
+        return hq::fail(ctx, HQ_E_INVAL, "hq_wire_decode_dev: NULL argument");
+    const uint64_t blocks = (n_spans + kWaves - 1) / kWaves;
+    if (blocks > 0x7FFFFFFFull)
+        return hq::fail(ctx, HQ_E_INVAL, "hq_wire_decode_dev: more than 2^33 spans");
+    int rc = hq::pre_launch(ctx);
+    if (rc) return rc;
+    DecodeK k{};
+    k.bytes = bytes;
+    k.len = len;
+    k.spans = spans;
+    k.n_spans = n_spans;
+    k.out = out;
+    k.status = status;
+    k.n_messages = n_messages;
+    hipLaunchKernelGGL(k_wire_decode<false>, dim3((uint32_t)blocks), dim3(kThreads), 0, ctx->stream,
+                       k);
+    return hq::post_launch(ctx, "hq_wire_decode_dev");
+}
+
+// ------------------------------------------------------------------- the device mode ----------
+struct hq_wire_dev {
+    hq_worker *worker = nullptr;
+    hq_ctx *ctx = nullptr;
+    std::string err;
+    // the queued batches: spans with absolute device addresses (the decode kernel's bytes = 0)
+    std::vector<hq_wire_span> spans;
+    std::vector<uint32_t> span_batch;
+    std::vector<uint32_t> batch_index;                // hq_wire_add_batch's call index
+    std::vector<uint64_t> batch_len;
+    uint64_t n_msgs = 0;
+    std::vector<StageBlock> stage;
+    std::vector<uint32_t> rejected;
+    // the handle table: built from the worker's groups, extended when it has gained some
+    std::vector<Slot> slots;
+    uint64_t known = 0;                               // handles in the table
+    bool has_empty = false;
+    uint32_t empty_val = 0;
+    DevBuf d_slots, d_spans, d_span_batch, d_bad, d_recs, d_cids, d_keys, d_vals, d_events, d_offsets,
+        d_counters, d_tmp;
+    uint64_t *h_read = nullptr;                       // pinned: the counters and the rows' count
+    uint32_t *h_bad = nullptr;
+    size_t h_bad_cap = 0;
+
+    int fail(int code, const std::string &m) {
+        err = m;
+        return code;
+    }
+    int hip(hipError_t e, const char *what) {
+        if (e == hipSuccess) return HQ_OK;
+        return fail(e == hipErrorOutOfMemory ? HQ_E_NOMEM : HQ_E_DEVICE,
+                    std::string(what) + ": " + hipGetErrorString(e));
+    }
+    // a device buffer of at least `bytes` (contents not kept)
+    int ensure(DevBuf &b, size_t bytes) {
+        if (bytes <= b.cap) return HQ_OK;
+        if (b.p) (void)hipFree(b.p);
+        b.p = nullptr;
+        b.cap = 0;
+        const size_t want = std::max<size_t>(bytes + bytes / 2, 4096);
+        const int rc = hip(hipMalloc(&b.p, want), "hq_wire device buffer");
+        if (!rc) b.cap = want;
+        return rc;
+    }
+    void insert(uint64_t id, uint32_t h) {
+        if (id == kEmptyKey) {
+            if (!has_empty) {
+                has_empty = true;
+                empty_val = h;
+            }
+            return;
+        }
+        const uint64_t mask = slots.size() - 1;
+        uint64_t s = hash_id(id) & mask;
+        while (slots[s].key != kEmptyKey && slots[s].key != id) s = (s + 1) & mask;
+        if (slots[s].key == kEmptyKey) slots[s] = Slot{id, h, 0};
+    }
+    // the table holds every group of the worker (load <= 1/2); uploaded when it has changed
+    int extend(uint64_t G) {
+        if (G == known && d_slots.p) return HQ_OK;
+        size_t want = 1024;
+        while (want < 2 * G) want *= 2;
+        std::vector<uint64_t> ids(G);
+        int rc = hq_worker_cluster_ids(worker, 0, G, ids.data());
+        if (rc) return fail(rc, "hq_wire_step_device: the worker's groups");
+        if (want != slots.size()) {                   // (handles never change: rebuilt from them)
+            slots.assign(want, Slot{kEmptyKey, 0, 0});
+            has_empty = false;
+            known = 0;
+        }
+        for (uint64_t h = known; h < G; ++h) insert(ids[h], (uint32_t)h);
+        known = G;
+        rc = ensure(d_slots, slots.size() * sizeof(Slot));
+        if (!rc)
+            rc = hip(hipMemcpyAsync(d_slots.p, slots.data(), slots.size() * sizeof(Slot),
+                                    hipMemcpyHostToDevice, ctx->stream), "hq_wire table upload");
+        return rc;
+    }
+};
+
+namespace {
+
+// where the device reads host-visible memory (pinned or device memory), or NULL
+const uint8_t *device_view(const uint8_t *p) {
+    hipPointerAttribute_t at;
+    if (!p || hipPointerGetAttributes(&at, p) != hipSuccess) {
+        (void)hipGetLastError();                      // pageable memory reports an error: clear it
+        return nullptr;
+    }
+    if (at.type == hipMemoryTypeDevice) return p;
+    if (at.type != hipMemoryTypeHost || !at.devicePointer) return nullptr;
+    const char *hp = static_cast<const char *>(at.hostPointer ? at.hostPointer : (const void *)p);
+    return reinterpret_cast<const uint8_t *>(static_cast<const char *>(at.devicePointer) +
+                                             (reinterpret_cast<const char *>(p) - hp));
+}
+
+}  // namespace
+
+int hq_wire_dev_open(hq_worker *worker, hq_wire_dev **out) {
+    hq_ctx *ctx = hq_worker_device_ctx(worker);
+    if (!ctx || !out) return HQ_E_INVAL;
+    hq_wire_dev *d = new (std::nothrow) hq_wire_dev();
+    if (!d) return HQ_E_NOMEM;
+    d->worker = worker;
+    d->ctx = ctx;
+    int rc = d->hip(hipSetDevice(ctx->device), "hipSetDevice");
+    if (!rc) rc = d->hip(hipHostMalloc(reinterpret_cast<void **>(&d->h_read), 64, hipHostMallocDefault),
+                         "hq_wire pinned readback");
+    if (rc) {
+        delete d;
+        return rc;
+    }
+    *out = d;
+    return HQ_OK;
+}
+
+void hq_wire_dev_close(hq_wire_dev *d) {
+    if (!d) return;
+    (void)hipSetDevice(d->ctx->device);
+    (void)hipStreamSynchronize(d->ctx->stream);
+    for (DevBuf *b : {&d->d_slots, &d->d_spans, &d->d_span_batch, &d->d_bad, &d->d_recs, &d->d_cids,
+                      &d->d_keys, &d->d_vals, &d->d_events, &d->d_offsets, &d->d_counters, &d->d_tmp})
+        if (b->p) (void)hipFree(b->p);
+    for (StageBlock &s : d->stage)
+        if (s.host) (void)hipHostFree(s.host);
+    if (d->h_read) (void)hipHostFree(d->h_read);
+    if (d->h_bad) (void)hipHostFree(d->h_bad);
+    delete d;
+}
+
+const char *hq_wire_dev_error(const hq_wire_dev *d) { return d ? d->err.c_str() : ""; }
+
+void hq_wire_dev_reset(hq_wire_dev *d) {
+    d->spans.clear();
+    d->span_batch.clear();
+    d->batch_index.clear();
+    d->batch_len.clear();
+    d->n_msgs = 0;
+    d->rejected.clear();
+    for (StageBlock &s : d->stage) s.fill = 0;
+}
+
+int hq_wire_dev_add_batch(hq_wire_dev *d, const uint8_t *bytes, size_t len, const hq_wire_span *spans,
+                          uint64_t n_spans, uint64_t n_messages, uint32_t index) {
+    if (d->n_msgs + n_messages >= (1ull << 31))
+        return d->fail(HQ_E_STATE, "hq_wire_add_batch: a device step holds < 2^31 messages");
+    int rc = d->hip(hipSetDevice(d->ctx->device), "hipSetDevice");
+    if (rc) return rc;
+    const uint8_t *dev = device_view(bytes);
+    if (!dev) {                                       // any other memory: into the pinned staging
+        StageBlock *blk = nullptr;
+        for (StageBlock &s : d->stage)
+            if (s.cap - s.fill >= len + 16) blk = &s;
+        if (!blk) {
+            StageBlock s;
+            s.cap = std::max<size_t>(len + 16, size_t(4) << 20);
+            rc = d->hip(hipHostMalloc(reinterpret_cast<void **>(&s.host), s.cap, hipHostMallocDefault),
+                        "hq_wire pinned staging");
+            if (!rc)
+                rc = d->hip(hipHostGetDevicePointer(reinterpret_cast<void **>(&s.dev), s.host, 0),
+                            "hq_wire pinned staging");
+            if (rc) {
+                if (s.host) (void)hipHostFree(s.host);
+                return rc;
+            }
+            d->stage.push_back(s);
+            blk = &d->stage.back();
+        }
+        std::memcpy(blk->host + blk->fill, bytes, len);
+        dev = blk->dev + blk->fill;
+        blk->fill += (len + 15) & ~size_t(15);
+    }
+    const uint32_t b = (uint32_t)d->batch_index.size();
+    d->batch_index.push_back(index);
+    d->batch_len.push_back(len);
+    for (uint64_t i = 0; i < n_spans; ++i) {
+        hq_wire_span s = spans[i];
+        s.offset += reinterpret_cast<uintptr_t>(dev);
+        s.first += (uint32_t)d->n_msgs;
+        d->spans.push_back(s);
+        d->span_batch.push_back(b);
+    }
+    d->n_msgs += n_messages;
+    return HQ_OK;
+}
+
+int hq_wire_dev_step(hq_wire_dev *d, const hqs::WireEvent *locals, uint64_t n_locals,
+                     hq_step_output *out, uint64_t counters[4], const uint32_t **rejected,
+                     uint64_t *n_rejected, uint64_t *rejected_bytes) {
+    hq_ctx *ctx = d->ctx;
+    hipStream_t st = ctx->stream;
+    std::memset(out, 0, sizeof *out);
+    std::memset(counters, 0, 4 * sizeof(uint64_t));
+    d->rejected.clear();
+    *rejected = nullptr;
+    *n_rejected = *rejected_bytes = 0;
+    const uint64_t nm = d->n_msgs, N = nm + n_locals, nb = d->batch_index.size(),
+                   ns = d->spans.size();
+    uint64_t G = 0;
+    int rc = hq_worker_group_count(d->worker, &G);
+    if (rc) return d->fail(rc, "hq_wire_step_device: the worker's groups");
+    if (N == 0 || G == 0) return HQ_OK;
+    if (N >= (1ull << 31) || G >= (1ull << 30))
+        return d->fail(HQ_E_STATE, "hq_wire_step_device: a step holds < 2^31 records, a worker < 2^30 groups");
+    rc = d->hip(hipSetDevice(ctx->device), "hipSetDevice");
+    if (!rc) rc = d->extend(G);
+    // the device buffers of the step
+    size_t tmp = 0;
+    const uint32_t sentinel = (uint32_t)(G * 4);
+    int end_bit = 1;
+    while (end_bit < 32 && (sentinel >> end_bit)) ++end_bit;
+    if (!rc) rc = d->ensure(d->d_keys, 2 * N * 4);
+    if (!rc) rc = d->ensure(d->d_vals, 2 * N * 4);
+    uint32_t *keys_in = static_cast<uint32_t *>(d->d_keys.p), *keys_out = keys_in + N;
+    uint32_t *vals_in = static_cast<uint32_t *>(d->d_vals.p), *vals_out = vals_in + N;
+    if (!rc)
+        rc = d->hip(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp, keys_in, keys_out, vals_in,
+                                                       vals_out, (int)N, 0, end_bit, st),
+                    "hipcub sort size");
+    if (!rc) rc = d->ensure(d->d_tmp, tmp);
+    if (!rc) rc = d->ensure(d->d_spans, ns * sizeof(hq_wire_span));
+    if (!rc) rc = d->ensure(d->d_span_batch, ns * 4);
+    if (!rc) rc = d->ensure(d->d_bad, (nb + 1) * 4);
+    if (!rc) rc = d->ensure(d->d_recs, N * sizeof(hqs::WireEvent));
+    if (!rc) rc = d->ensure(d->d_cids, (nm + 1) * 8);
+    if (!rc) rc = d->ensure(d->d_events, N * sizeof(hq_event));
+    if (!rc) rc = d->ensure(d->d_offsets, (G + 1) * 8);
+    if (!rc) rc = d->ensure(d->d_counters, 64);
+    if (!rc && nb > d->h_bad_cap) {
+        if (d->h_bad) (void)hipHostFree(d->h_bad);
+        d->h_bad = nullptr;
+        d->h_bad_cap = 0;
+        rc = d->hip(hipHostMalloc(reinterpret_cast<void **>(&d->h_bad), nb * 2 * 4, hipHostMallocDefault),
+                    "hq_wire pinned readback");
+        if (!rc) d->h_bad_cap = nb * 2;
+    }
+    if (rc) return rc;
+    hqs::WireEvent *recs = static_cast<hqs::WireEvent *>(d->d_recs.p);
+    auto h2d = [&](void *dst, const void *src, size_t bytes) {
+        if (!rc && bytes)
+            rc = d->hip(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st), "hq_wire H2D");
+    };
+    h2d(d->d_spans.p, d->spans.data(), ns * sizeof(hq_wire_span));
+    h2d(d->d_span_batch.p, d->span_batch.data(), ns * 4);
+    h2d(recs + nm, locals, n_locals * sizeof(hqs::WireEvent));
+    if (!rc) rc = d->hip(hipMemsetAsync(d->d_bad.p, 0, (nb + 1) * 4, st), "memset");
+    if (!rc) rc = d->hip(hipMemsetAsync(d->d_counters.p, 0, 64, st), "memset");
+    if (rc) return rc;
+    // decode: the spans carry absolute addresses, so the buffer is all of memory
+    if (ns) {
+        DecodeK k{};
+        k.bytes = nullptr;
+        k.len = UINT64_MAX;
+        k.spans = static_cast<const hq_wire_span *>(d->d_spans.p);
+        k.n_spans = ns;
+        k.n_messages = nm;
+        k.span_batch = static_cast<const uint32_t *>(d->d_span_batch.p);
+        k.bad = static_cast<uint32_t *>(d->d_bad.p);
+        k.recs = recs;
+        k.cids = static_cast<uint64_t *>(d->d_cids.p);
+        rc = hq::pre_launch(ctx);
+        if (rc) return d->fail(rc, ctx->err);
+        hipLaunchKernelGGL(k_wire_decode<true>, dim3((uint32_t)((ns + kWaves - 1) / kWaves)),
+                           dim3(kThreads), 0, st, k);
+        rc = hq::post_launch(ctx, "k_wire_decode");
+        if (rc) return d->fail(rc, ctx->err);
+    }
+    KeysK kk{};
+    kk.recs = recs;
+    kk.cids = static_cast<const uint64_t *>(d->d_cids.p);
+    kk.bad = static_cast<const uint32_t *>(d->d_bad.p);
+    kk.n_msgs = nm;
+    kk.n = N;
+    kk.slots = static_cast<const Slot *>(d->d_slots.p);
+    kk.n_slots = d->slots.size();
+    kk.has_empty = d->has_empty;
+    kk.empty_val = d->empty_val;
+    kk.sentinel = sentinel;
+    kk.keys = keys_in;
+    kk.vals = vals_in;
+    kk.counters = static_cast<unsigned long long *>(d->d_counters.p);
+    uint64_t *offsets = static_cast<uint64_t *>(d->d_offsets.p);
+    hq_event *events = static_cast<hq_event *>(d->d_events.p);
+    rc = hq::pre_launch(ctx);
+    if (rc) return d->fail(rc, ctx->err);
+    hipLaunchKernelGGL(k_wire_keys, dim3((uint32_t)((N + 255) / 256)), dim3(256), 0, st, kk);
+    rc = hq::post_launch(ctx, "k_wire_keys");
+    // stable, over the bits the key needs: node.handleEvents order per handle, arrival order
+    // within a category
+    if (!rc)
+        rc = hq::check_hip(ctx, hipcub::DeviceRadixSort::SortPairs(d->d_tmp.p, tmp, keys_in, keys_out,
+                                                                   vals_in, vals_out, (int)N, 0,
+                                                                   end_bit, st), "hipcub sort");
+    if (!rc) {
+        hipLaunchKernelGGL(k_wire_offsets, dim3((uint32_t)((G + 1 + 255) / 256)), dim3(256), 0, st,
+                           keys_out, N, G, offsets);
+        rc = hq::post_launch(ctx, "k_wire_offsets");
+    }
+    if (!rc) {
+        hipLaunchKernelGGL(k_wire_rows, dim3((uint32_t)((N + 255) / 256)), dim3(256), 0, st, recs,
+                           vals_out, offsets + G, events);
+        rc = hq::post_launch(ctx, "k_wire_rows");
+    }
+    // the counters, the rows' count and the batches' flags back: the step's size is the host's to
+    // know (the device step sizes its buffers by it)
+    if (!rc)
+        rc = hq::check_hip(ctx, hipMemcpyAsync(d->h_read, d->d_counters.p, 32, hipMemcpyDeviceToHost, st),
+                           "hq_wire D2H");
+    if (!rc)
+        rc = hq::check_hip(ctx, hipMemcpyAsync(d->h_read + 4, offsets + G, 8, hipMemcpyDeviceToHost, st),
+                           "hq_wire D2H");
+    if (!rc && nb)
+        rc = hq::check_hip(ctx, hipMemcpyAsync(d->h_bad, d->d_bad.p, nb * 4, hipMemcpyDeviceToHost, st),
+                           "hq_wire D2H");
+    if (!rc) rc = hq::check_hip(ctx, hipStreamSynchronize(st), "hq_wire sync");
+    if (rc) return d->fail(rc, ctx->err);
+    for (int k = 0; k < 4; ++k) counters[k] = d->h_read[k];
+    for (uint64_t b = 0; b < nb; ++b)
+        if (d->h_bad[b]) {
+            d->rejected.push_back(d->batch_index[b]);
+            *rejected_bytes += d->batch_len[b];
+        }
+    *rejected = d->rejected.data();
+    *n_rejected = d->rejected.size();
+    const uint64_t n_rows = d->h_read[4];
+    if (n_rows == 0) return HQ_OK;
+    rc = hq_worker_step_device_rows(d->worker, G, nullptr, offsets, events, n_rows, out);
+    if (rc) return d->fail(rc, hq_worker_last_error(d->worker));
+    return HQ_OK;
+}

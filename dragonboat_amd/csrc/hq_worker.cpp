@@ -1146,6 +1146,28 @@ int hq_worker_step(hq_worker *w, const hq_step_input *in, hq_step_output *out) {
 
 }  // extern "C"
 
+// the wire's device mode (hq_wire_dev.hip; declared in hq_dstep.h)
+hq_ctx *hq_worker_device_ctx(hq_worker *w) { return w && w->dstep ? w->ctx : nullptr; }
+
+int hq_worker_cluster_ids(hq_worker *w, uint64_t h0, uint64_t n, uint64_t *out) {
+    if (!w || h0 > w->groups.size() || n > w->groups.size() - h0 || (n && !out)) return HQ_E_INVAL;
+    for (uint64_t i = 0; i < n; ++i) out[i] = w->groups[h0 + i].cluster_id;
+    return HQ_OK;
+}
+
+int hq_worker_step_device_rows(hq_worker *w, uint64_t n, const uint32_t *groups,
+                               const uint64_t *offsets, const hq_event *events, uint64_t n_events,
+                               hq_step_output *out) {
+    if (!w || !out) return HQ_E_INVAL;
+    if (!w->dstep) return w->fail(HQ_E_INVAL, "hq_worker_step: not a device worker");
+    if (n && !offsets) return w->fail(HQ_E_INVAL, "hq_worker_step: NULL offsets");
+    std::memset(out, 0, sizeof *out);
+    hq_dstep_in in{n, groups, offsets, events, nullptr, nullptr};
+    in.n_events = n_events;
+    in.on_device = true;
+    return w->step_on_device(in, out);
+}
+
 // hq_worker_step_jobs (hq_jobs.cpp): jobs that are all sized event streams for distinct device
 // workers on one GPU are stepped through shared launches (hq_dstep_run_jobs: one pass A per
 // input chunk, one layout, one k_step_lite and one pass B for all of them, one wait) instead of

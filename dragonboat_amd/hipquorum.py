@@ -188,6 +188,12 @@ HQ_RPC_BIN_VERSION = 210
 WIRE_MESSAGE_DTYPE = np.dtype([("ev", EVENT_DTYPE), ("cluster_id", "<u8"), ("to", "<u8"),
                                ("log_term", "<u8"), ("commit", "<u8"), ("n_entries", "<u4"),
                                ("has_snapshot", "<u4")], align=True)
+# wire decode on the device: hq_wire_span (hq_wire_frame_batch -> hq_wire_decode_dev)
+HQ_WIRE_SPAN_MESSAGES = 64
+HQ_WIRE_SPAN_BYTES = 4096
+HQ_WIRE_SPAN_LARGE = 1
+WIRE_SPAN_DTYPE = np.dtype([("offset", "<u8"), ("len", "<u8"), ("first", "<u4"),
+                            ("count", "<u2"), ("flags", "<u2")], align=True)
 
 
 class WireBatchInfo(ctypes.Structure):
@@ -440,6 +446,13 @@ SIGNATURES = {
     "hq_wire_add_locals": (ctypes.c_int, [_vp, ctypes.c_uint64, _vp, _vp, _vp]),
     "hq_wire_step_sized": (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, _vp, ctypes.c_uint64,
                                           ctypes.POINTER(StepStream), ctypes.POINTER(WireStats)]),
+    "hq_wire_frame_batch": (ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.c_uint64, _vp,
+                                           ctypes.c_uint64, _u64p, ctypes.POINTER(WireBatchInfo)]),
+    "hq_wire_decode_dev": (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, _vp, ctypes.c_uint64, _vp, _vp,
+                                          ctypes.c_uint64]),
+    "hq_wire_attach_device": (ctypes.c_int, [_vp, _vp]),
+    "hq_wire_step_device": (ctypes.c_int, [_vp, _vp, ctypes.POINTER(WireStats)]),
+    "hq_wire_device_rejected": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), _u64p]),
     "hq_worker_group_count": (ctypes.c_int, [_vp, _u64p]),
     "hq_synth_commit_dev": (ctypes.c_int, [_vp, ctypes.POINTER(SynthSpec), ctypes.POINTER(CommitArgs)]),
     "hq_synth_commit_lag_dev": (ctypes.c_int, [_vp, ctypes.POINTER(SynthSpec),
@@ -1863,6 +1876,57 @@ def decode_batch(data: bytes):
     return out[:n.value], info
 
 
+def frame_batch(data: bytes, base: int = 0, first: int = 0):
+    """hq_wire_frame_batch: (WIRE_SPAN_DTYPE array, WireBatchInfo) of one MessageBatch, framed on
+    the host without looking into a message. The spans' offsets count from `base` and their first
+    message indices from `first` (where the batch lies in a buffer and a record array that hold
+    several)."""
+    buf = np.frombuffer(data, np.uint8)
+    n = ctypes.c_uint64(0)
+    info = WireBatchInfo()
+    _chk(lib.hq_wire_frame_batch(_p(buf), len(data), base, None, 0, ctypes.byref(n),
+                                 ctypes.byref(info)), "hq_wire_frame_batch")
+    spans = np.zeros(n.value, WIRE_SPAN_DTYPE)
+    _chk(lib.hq_wire_frame_batch(_p(buf), len(data), base, _p(spans) if n.value else None, n.value,
+                                 ctypes.byref(n), ctypes.byref(info)), "hq_wire_frame_batch")
+    spans["first"] += np.uint32(first)
+    return spans, info
+
+
+def decode_dev(ctx: Context, data, spans, n_messages: int, data_len: Optional[int] = None):
+    """hq_wire_decode_dev: the messages of `spans` (WIRE_SPAN_DTYPE, host or device) decoded on the
+    device from `data` (a DeviceArray or address, or a pinned uint8 array read in place; any other
+    host bytes are uploaded). Returns (WIRE_MESSAGE_DTYPE array, uint8 status array), copied back
+    after the stream is drained."""
+    owned = []
+    if isinstance(data, (bytes, bytearray)):
+        data = np.frombuffer(bytes(data), np.uint8)
+    if isinstance(data, np.ndarray):
+        data_len = len(data) if data_len is None else data_len
+        if len(data) and pointer_kind(data) != HQ_PTR_PINNED_HOST:
+            data = ctx.upload(data)
+            owned.append(data)
+    elif isinstance(data, DeviceArray) and data_len is None:
+        data_len = data.count
+    if isinstance(spans, np.ndarray):
+        n_spans = len(spans)
+        spans = ctx.upload(np.ascontiguousarray(spans, WIRE_SPAN_DTYPE))
+        owned.append(spans)
+    else:
+        n_spans = spans.count
+    out = ctx.empty(n_messages, WIRE_MESSAGE_DTYPE)
+    status = ctx.empty(n_messages, np.uint8)
+    owned += [out, status]
+    try:
+        ctx._check(lib.hq_wire_decode_dev(ctx.h, _p(data) if data_len else None, data_len or 0,
+                                          _p(spans), n_spans, _p(out), _p(status), n_messages))
+        return ctx.download(out), ctx.download(status)
+    finally:
+        ctx.sync()
+        for a in owned:
+            ctx.free(a)
+
+
 def encode_wire_batch(msgs, deployment_id=0, source_address=b"", out=None):
     """hq_wire_encode_batch: one MessageBatch of WIRE_MESSAGE_DTYPE messages (no entries), as
     the sending node marshals it. Into `out` (uint8, e.g. pinned) when given: returns the bytes
@@ -1923,6 +1987,34 @@ class Wire:
     def attach(self, worker: "Worker") -> None:
         """hq_wire_attach: messages resolved to the worker's handles as they are decoded."""
         self._check(lib.hq_wire_attach(self.h, worker.h if worker else None), "hq_wire_attach")
+
+    def attach_device(self, worker) -> None:
+        """hq_wire_attach_device: the device mode (worker: on_device=True). Batches are framed on
+        the host and decoded, keyed and sorted on the device by step_device."""
+        self._check(lib.hq_wire_attach_device(self.h, worker.h if worker else None),
+                    "hq_wire_attach_device")
+        self._dev_worker = worker
+
+    def step_device(self, copy=True):
+        """hq_wire_step_device: (results as Worker.step returns them, WireStats). With copy=False
+        the arrays are views of the worker's buffers, valid until its next step."""
+        out, st = StepOutput(), WireStats()
+        self._check(lib.hq_wire_step_device(self.h, ctypes.byref(out), ctypes.byref(st)),
+                    "hq_wire_step_device")
+        n = ctypes.c_uint64(0)
+        _chk(lib.hq_worker_group_count(self._dev_worker.h, ctypes.byref(n)), "hq_worker_group_count")
+        return Worker._results(out, copy, n.value), st
+
+    def device_rejected(self) -> np.ndarray:
+        """hq_wire_device_rejected: the add_batch call indices (since the last reset) of the
+        batches the last step_device dropped for a malformed message."""
+        p, n = _vp(), ctypes.c_uint64(0)
+        self._check(lib.hq_wire_device_rejected(self.h, ctypes.byref(p), ctypes.byref(n)),
+                    "hq_wire_device_rejected")
+        if not n.value:
+            return np.zeros(0, np.uint32)
+        buf = (ctypes.c_char * (4 * n.value)).from_address(p.value)
+        return np.frombuffer(buf, np.uint32).copy()
 
     def step_sized(self, data: np.ndarray, sizes16: np.ndarray):
         """hq_wire_step_sized into the caller's buffers (uint8 `data`, uint16 `sizes16`, e.g.

@@ -1363,6 +1363,84 @@ int hq_wire_attach(hq_wire *w, hq_worker *worker);
 int hq_wire_step_sized(hq_wire *w, uint8_t *bytes, uint64_t cap, uint16_t *sizes16, uint64_t n_cap,
                        hq_step_stream *out, hq_wire_stats *stats);
 
+/* ---------------------------------------------------------------- wire decode on the device -- */
+/*
+ * The same decode with the per-message work on the GPU. The host only frames a batch
+ * (hq_wire_frame_batch: one header hop per message, nothing read inside one) into spans; the
+ * device decodes every message of every span (hq_wire_decode_dev). Additions to ABI 21 (new
+ * symbols only).
+ *
+ * A span is a run of at most HQ_WIRE_SPAN_MESSAGES consecutive `requests` fields of one batch,
+ * back to back (tag, length, body; nothing between them), of at most HQ_WIRE_SPAN_BYTES bytes
+ * together: one wave's work, and what it keeps of the batch in LDS. A single message longer than
+ * HQ_WIRE_SPAN_BYTES is a span by itself, flagged HQ_WIRE_SPAN_LARGE (decoded by one lane straight
+ * from memory). Any other field of the batch between two messages ends a span.
+ */
+#define HQ_WIRE_SPAN_MESSAGES 64u
+#define HQ_WIRE_SPAN_BYTES    4096u
+#define HQ_WIRE_SPAN_LARGE    1u     /* hq_wire_span.flags: one message over HQ_WIRE_SPAN_BYTES */
+
+typedef struct hq_wire_span {
+    uint64_t offset;              /* of the first message's tag byte: base + position in the batch */
+    uint64_t len;                 /* bytes, tags and lengths included */
+    uint32_t first;               /* index in the batch of the span's first message */
+    uint16_t count;               /* messages, 1 .. HQ_WIRE_SPAN_MESSAGES */
+    uint16_t flags;               /* HQ_WIRE_SPAN_* */
+} hq_wire_span;
+
+/* Stateless, host only: frame one MessageBatch. The batch is walked as hq_wire_decode_batch walks
+ * it (any field order, unknown fields skipped; the same framing errors are HQ_E_INVAL) but no
+ * message is looked into, so a batch hq_wire_decode_batch accepts is accepted here with the same
+ * *info, and a batch rejected here is rejected there. The spans go to spans[0 .. min(*n_spans,
+ * cap)) (spans may be NULL to count), their offsets counted from `base` (where the batch will
+ * lie in the buffer the device reads); HQ_E_STATE if they do not fit cap. info may be NULL. */
+int hq_wire_frame_batch(const uint8_t *bytes, size_t len, uint64_t base, hq_wire_span *spans,
+                        uint64_t cap, uint64_t *n_spans, hq_wire_batch_info *info);
+
+/* Decode the messages of spans[0 .. n_spans) on the device, asynchronously on ctx's stream. bytes
+ * is device memory, or pinned host memory the device reads in place (hq_alloc_pinned); spans, out
+ * and status are device memory. Message k of a span (in the span's order) goes to index
+ * i = span.first + k (a caller that concatenates batches adds each batch's first index to its
+ * spans' `first`); indices at or past n_messages are not written. status[i] = 0 and out[i] =
+ * what hq_wire_decode_batch writes for that message, field for field; or status[i] = 1 for a
+ * message that decoder rejects (out[i] is then unspecified), and for every message of a span whose
+ * headers are not where the span says (a span that was not framed from these bytes).
+ *
+ * The bytes are not trusted: every loop is bounded by the message's length, no byte outside
+ * [span.offset, span.offset + span.len) is read (no slack is needed behind the buffer), and a
+ * span that does not lie within bytes[0 .. len), or holds more than HQ_WIRE_SPAN_MESSAGES
+ * messages, or more than HQ_WIRE_SPAN_BYTES bytes without being HQ_WIRE_SPAN_LARGE, is skipped
+ * with status 1 for its messages. */
+int hq_wire_decode_dev(hq_ctx *ctx, const uint8_t *bytes, uint64_t len, const hq_wire_span *spans,
+                       uint64_t n_spans, hq_wire_message *out, uint8_t *status,
+                       uint64_t n_messages);
+
+/* The device mode of hq_wire. hq_wire_attach_device binds a device worker (HQ_WORKER_ON_DEVICE;
+ * any other worker is HQ_E_INVAL, events queued HQ_E_STATE); from then on, each step:
+ *   hq_wire_reset;
+ *   hq_wire_add_batch frames the batch on the host and checks its deployment id and binary version
+ *     exactly as before (a foreign batch is dropped and counted, a framing error is HQ_E_INVAL at
+ *     once) and queues its spans. Bytes the device can read in place (hq_alloc_pinned, or device
+ *     memory) are referenced, not copied: THEY MUST STAY VALID AND UNCHANGED UNTIL
+ *     hq_wire_step_device RETURNS. Any other memory is copied into the wire's pinned staging;
+ *   hq_wire_add_local / hq_wire_add_locals queue local events as before;
+ *   hq_wire_step_device decodes every queued message on the device, resolves its cluster to the
+ *     worker's handle through a device hash table (built from the worker's groups, extended when
+ *     it has gained some), sorts the records with the local ones by (handle, node.handleEvents
+ *     category) in arrival order, and steps the worker over the rows, which never leave the
+ *     device. *out is what hq_worker_step returns for the same events (valid until the worker's
+ *     next step; deferred indices count the events in handle order), *stats what the host-attached
+ *     wire reports for the same calls.
+ * A batch whose framing is valid but which holds a malformed message is dropped whole at the
+ * step (none of its messages reaches a group) and counted nowhere in *stats, as a batch
+ * hq_wire_add_batch rejects; hq_wire_device_rejected lists such batches of the last step as the
+ * indices of their hq_wire_add_batch call since the last hq_wire_reset (array owned by w until
+ * its next step or reset). hq_wire_step_input / _step_stream / _step_sized are HQ_E_STATE in this
+ * mode; hq_wire_attach returns to the host mode. */
+int hq_wire_attach_device(hq_wire *w, hq_worker *worker);
+int hq_wire_step_device(hq_wire *w, hq_step_output *out, hq_wire_stats *stats);
+int hq_wire_device_rejected(hq_wire *w, const uint32_t **batches, uint64_t *n);
+
 /* ---------------------------------------------------------------- synthetic inputs ---------- */
 
 /*
