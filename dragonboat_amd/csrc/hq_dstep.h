@@ -103,6 +103,16 @@ int hq_dstep_put(hq_dstep *d, uint64_t g0, uint64_t ng, const hq_dgroup *g, cons
                  uint64_t m0, uint64_t nm, const hq_dmember *m);
 // copy the first ng group records (with their reads) and nm member records back
 int hq_dstep_get(hq_dstep *d, uint64_t ng, hq_dgroup *g, hq_dread *r, uint64_t nm, hq_dmember *m);
+// the resident state as it stands, for a read-only kernel queued on ctx's stream (hq_heartbeat.hip);
+// the pointers hold until the next hq_dstep_put
+struct hq_dstate_view {
+    hq_ctx *ctx;
+    const hq_dgroup *groups;
+    const hq_dread *reads;            // kDReads per group
+    const hq_dmember *members;
+    uint64_t n_groups;                // group records uploaded (valid handles)
+};
+void hq_dstep_view(hq_dstep *d, hq_dstate_view *out);
 // one step over the device state; the kernels check the input (out->input_error)
 int hq_dstep_run(hq_dstep *d, const hq_dstep_in *in, hq_dstep_out *out);
 // several engines' steps through shared launches (hq_worker_step_jobs): every input a sized

@@ -2000,6 +2000,10 @@ int hq_dstep_get(hq_dstep *d, uint64_t ng, hq_dgroup *g, hq_dread *r, uint64_t n
     return rc;
 }
 
+void hq_dstep_view(hq_dstep *d, hq_dstate_view *out) {
+    *out = hq_dstate_view{d->ctx, d->groups, d->reads, d->members, d->n_groups};
+}
+
 namespace {
 
 // One worker's step from its preparation to its outputs (hq_dstep_run; hq_dstep_run_jobs runs

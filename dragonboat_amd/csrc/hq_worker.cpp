@@ -27,6 +27,7 @@
 
 #include "../../include/hipquorum.h"
 #include "hq_dstep.h"
+#include "hq_heartbeat.h"
 
 namespace {
 
@@ -101,6 +102,10 @@ struct hq_worker {
     uint64_t dev_groups = 0, dev_members = 0;   // records already on the device
     std::vector<uint32_t> dirty;          // handles changed on the host since the last upload
     hq_dstep_out dout{};
+    hq_hb_dev *hb = nullptr;              // device worker: hq_worker_heartbeats' buffers (first call)
+    std::vector<uint32_t> hb_words;       // host worker: its heartbeat output
+    std::vector<hq_heartbeat_lag> hb_lags;
+    std::vector<hq_heartbeat_ctx> hb_ctxs;
     std::vector<hq_event> decoded;        // host worker: a stream step's rows
     std::vector<uint64_t> sized_off, sized_boff;   // host worker: a sized stream's prefixes
     std::vector<uint32_t> sized_groups;            // and its implicit handles
@@ -169,6 +174,7 @@ struct hq_worker {
                          uint64_t t1);
     int load_group(Group &g, const hq_worker_group *src, const hq_member *m, bool fresh);
     int step(const hq_step_input *in, hq_step_output *out);
+    int heartbeats(uint64_t n, const uint32_t *list, hq_heartbeat_output *out);
     Verdict handle(Group &g, const hq_event &e, uint64_t ei);
     Verdict read_index(Group &g, uint64_t from, uint64_t low, uint64_t high, uint64_t ei);
     void advance(Group &g);
@@ -952,8 +958,137 @@ int hq_worker::device_step_done(int rc, const hq_dstep_in &inp, hq_step_output *
     return HQ_OK;
 }
 
+// ------------------------------------------------------------------------------ heartbeats ---
+// broadcastHeartbeatMessage (raft.go:826-848) for the listed groups. A device worker's state is
+// read where it lives (hq_heartbeat.hip); a host worker's here, into the same compact output.
+int hq_worker::heartbeats(uint64_t n, const uint32_t *list, hq_heartbeat_output *out) {
+    if (dstep) {
+        int rc = sync_to_device();
+        if (rc) return rc;
+        std::memset(out, 0, sizeof *out);
+        if (n == 0) return HQ_OK;
+        if (!hb && (rc = hq(hq_hb_dev_open(ctx, &hb), "hq_worker_heartbeats"))) return rc;
+        hq_dstate_view st;
+        hq_dstep_view(dstep, &st);
+        uint32_t e = 0;
+        rc = hq_hb_dev_run(hb, &st, dev_members, n, list, out, &e);
+        if (rc == HQ_E_INVAL && e)
+            return e & kHbErrHandle
+                       ? fail(HQ_E_INVAL, "hq_worker_heartbeats: unknown group handle")
+                       : fail(HQ_E_STATE, "hq_worker_heartbeats: a resident group record is out of "
+                                          "range (internal)");
+        return hq(rc, "hq_worker_heartbeats");
+    }
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint64_t h = list ? list[i] : i;
+        if (h >= groups.size()) return fail(HQ_E_INVAL, "hq_worker_heartbeats: unknown group handle");
+        if (groups[h].n_members > kDMembers)
+            return fail(HQ_E_INVAL, "hq_worker_heartbeats: a group of more than 16 members");
+    }
+    hb_words.assign(n, 0);
+    hb_lags.clear();
+    hb_ctxs.clear();
+    uint64_t msgs = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        const Group &g = groups[list ? list[i] : i];
+        if (g.state != HQ_STATE_LEADER || g.has(kSuspended)) continue;
+        const ReadQueue *q = g.rq == kNone ? nullptr : &rqs[g.rq];
+        uint64_t lo = 0, hi = 0;                    // readIndex.peepCtx: the queue's tail
+        if (q && q->n) {
+            lo = q->r[q->n - 1].low;
+            hi = q->r[q->n - 1].high;
+        }
+        const bool zero_ctx = (lo | hi) == 0;
+        // pool order: the node, the other voting members, the observers (with a zero ctx)
+        const Member *m = pool.data() + g.mem;
+        const uint32_t end = zero_ctx ? g.n_members : g.n_voting;
+        uint32_t word = 0;
+        uint64_t match_of[kDMembers] = {};
+        for (uint32_t s = 1; s < end; ++s) {
+            const uint32_t bit = 1u << m[s].order;
+            word |= bit | (m[s].match < g.committed ? bit << 16 : 0u);
+            match_of[m[s].order] = m[s].match;
+        }
+        hb_words[i] = word;
+        for (uint32_t o = 0; o < kDMembers; ++o) {
+            msgs += (word >> o) & 1;
+            if ((word >> (16 + o)) & 1) hb_lags.push_back({(uint32_t)i, o, match_of[o]});
+        }
+        if (word && !zero_ctx) hb_ctxs.push_back({lo, hi, (uint32_t)i, 0});
+    }
+    std::memset(out, 0, sizeof *out);
+    out->words = hb_words.data();
+    out->n_groups = n;
+    out->lags = hb_lags.data();
+    out->n_lags = hb_lags.size();
+    out->ctxs = hb_ctxs.data();
+    out->n_ctxs = hb_ctxs.size();
+    out->n_messages = msgs;
+    return HQ_OK;
+}
+
 // ------------------------------------------------------------------------------ C-ABI ------
 extern "C" {
+
+int hq_worker_heartbeats(hq_worker *w, uint64_t n_groups, const uint32_t *groups,
+                         hq_heartbeat_output *out) {
+    if (!w) return HQ_E_INVAL;
+    if (!out) return w->fail(HQ_E_INVAL, "hq_worker_heartbeats: out is NULL");
+    if (n_groups >= (uint64_t(1) << 28))
+        return w->fail(HQ_E_INVAL, "hq_worker_heartbeats: 2^28 or more groups in one call");
+    if (!groups && n_groups > w->groups.size())
+        return w->fail(HQ_E_INVAL, "hq_worker_heartbeats: unknown group handle");
+    return w->heartbeats(n_groups, groups, out);
+}
+
+int hq_heartbeats_expand(const hq_heartbeat_output *hb, const uint64_t *cluster_id,
+                         const uint64_t *term, const uint64_t *committed, const uint32_t *n_members,
+                         const uint64_t *member_ids, hq_heartbeat_msg *msgs, uint64_t cap,
+                         uint64_t *n) {
+    if (!hb || !n) return HQ_E_INVAL;
+    const uint64_t G = hb->n_groups;
+    if (G && (!hb->words || !cluster_id || !term || !committed || !n_members || !member_ids))
+        return HQ_E_INVAL;
+    if ((hb->n_lags && !hb->lags) || (hb->n_ctxs && !hb->ctxs)) return HQ_E_INVAL;
+    // the checks first (nothing is written for an inconsistent input), then the messages
+    for (int write = 0; write < 2; ++write) {
+        uint64_t li = 0, ci = 0, k = 0;
+        for (uint64_t pos = 0; pos < G; ++pos) {
+            const uint32_t w = hb->words[pos], to = w & 0xFFFFu, behind = w >> 16;
+            if (!write) {
+                if (behind & ~to) return HQ_E_INVAL;
+                if (n_members[pos] > kDMembers || (to >> n_members[pos])) return HQ_E_INVAL;
+            }
+            uint64_t lo = 0, hi = 0;
+            if (ci < hb->n_ctxs && hb->ctxs[ci].pos == pos) {
+                lo = hb->ctxs[ci].ctx_low;
+                hi = hb->ctxs[ci].ctx_high;
+                if (!write && (!w || (lo | hi) == 0)) return HQ_E_INVAL;
+                ++ci;
+            }
+            for (uint32_t o = 0; o < kDMembers; ++o) {
+                if (!((to >> o) & 1)) continue;
+                uint64_t commit = committed[pos];
+                if ((behind >> o) & 1) {
+                    if (li >= hb->n_lags || hb->lags[li].pos != pos || hb->lags[li].member != o)
+                        return HQ_E_INVAL;
+                    commit = hb->lags[li++].match;
+                }
+                if (write)
+                    msgs[k] = hq_heartbeat_msg{cluster_id[pos], member_ids[pos * kDMembers + o],
+                                               term[pos], commit, lo, hi};
+                ++k;
+            }
+        }
+        if (!write) {
+            // (records left over: out of order, for a position outside the list, or without a bit)
+            if (li != hb->n_lags || ci != hb->n_ctxs || k != hb->n_messages) return HQ_E_INVAL;
+            *n = k;
+            if (k > cap || (k && !msgs)) return HQ_E_STATE;
+        }
+    }
+    return HQ_OK;
+}
 
 int hq_worker_open(int device, uint32_t n_max, hq_worker **out) {
     return hq_worker_open_ex(device, n_max, 0, out);
@@ -997,6 +1132,7 @@ int hq_worker_open_ex(int device, uint32_t n_max, uint32_t flags, hq_worker **ou
 
 void hq_worker_close(hq_worker *w) {
     if (!w) return;
+    if (w->hb) hq_hb_dev_close(w->hb);
     if (w->dstep) hq_dstep_close(w->dstep);
     if (w->ctx) {
         hq_sync(w->ctx);

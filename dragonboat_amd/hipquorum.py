@@ -196,6 +196,24 @@ WIRE_SPAN_DTYPE = np.dtype([("offset", "<u8"), ("len", "<u8"), ("first", "<u4"),
                             ("count", "<u2"), ("flags", "<u2")], align=True)
 
 
+# leader heartbeat broadcast (include/hipquorum.h; hq_worker_heartbeats / hq_heartbeats_expand)
+HQ_MSG_HEARTBEAT = 17
+HEARTBEAT_LAG_DTYPE = np.dtype([("pos", "<u4"), ("member", "<u4"), ("match", "<u8")], align=True)
+HEARTBEAT_CTX_DTYPE = np.dtype([("ctx_low", "<u8"), ("ctx_high", "<u8"), ("pos", "<u4"),
+                                ("reserved", "<u4")], align=True)
+HEARTBEAT_MSG_DTYPE = np.dtype([("cluster_id", "<u8"), ("to", "<u8"), ("term", "<u8"),
+                                ("commit", "<u8"), ("hint", "<u8"), ("hint_high", "<u8")],
+                               align=True)
+
+
+class HeartbeatOutput(ctypes.Structure):
+    """Mirror of ``hq_heartbeat_output``."""
+
+    _fields_ = [("words", _vp), ("n_groups", ctypes.c_uint64), ("lags", _vp),
+                ("n_lags", ctypes.c_uint64), ("ctxs", _vp), ("n_ctxs", ctypes.c_uint64),
+                ("n_messages", ctypes.c_uint64), ("gpu_ns", ctypes.c_uint64)]
+
+
 class WireBatchInfo(ctypes.Structure):
     _fields_ = [("n_messages", ctypes.c_uint64), ("deployment_id", ctypes.c_uint64),
                 ("source_address_len", ctypes.c_uint64), ("bin_ver", ctypes.c_uint32),
@@ -454,6 +472,10 @@ SIGNATURES = {
     "hq_wire_step_device": (ctypes.c_int, [_vp, _vp, ctypes.POINTER(WireStats)]),
     "hq_wire_device_rejected": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), _u64p]),
     "hq_worker_group_count": (ctypes.c_int, [_vp, _u64p]),
+    "hq_worker_heartbeats": (ctypes.c_int, [_vp, ctypes.c_uint64, _vp,
+                                            ctypes.POINTER(HeartbeatOutput)]),
+    "hq_heartbeats_expand": (ctypes.c_int, [ctypes.POINTER(HeartbeatOutput), _vp, _vp, _vp, _vp,
+                                            _vp, _vp, ctypes.c_uint64, _u64p]),
     "hq_synth_commit_dev": (ctypes.c_int, [_vp, ctypes.POINTER(SynthSpec), ctypes.POINTER(CommitArgs)]),
     "hq_synth_commit_lag_dev": (ctypes.c_int, [_vp, ctypes.POINTER(SynthSpec),
                                                ctypes.POINTER(LagArgs), _vp]),
@@ -1584,6 +1606,37 @@ class Worker:
         self._check(lib.hq_worker_add_groups(self.h, _p(groups), len(groups), _p(members)),
                     "hq_worker_add_groups")
 
+    def group_count(self) -> int:
+        n = ctypes.c_uint64(0)
+        self._check(lib.hq_worker_group_count(self.h, ctypes.byref(n)), "hq_worker_group_count")
+        return n.value
+
+    def heartbeats(self, groups=None, copy=True):
+        """hq_worker_heartbeats: what the leaders among `groups` (uint32 handles, repeats allowed;
+        None: every handle in order) send on a LeaderHeartbeat tick, in their state at the call.
+        Returns a dict: 'words' (uint32 per listed group), 'lags' (HEARTBEAT_LAG_DTYPE), 'ctxs'
+        (HEARTBEAT_CTX_DTYPE), 'n_messages', 'gpu_ns'; heartbeats_expand writes the messages.
+        With copy=False the arrays are views of the worker's buffers, valid until its next
+        heartbeats call."""
+        if groups is None:
+            n, gp = self.group_count(), None
+        else:
+            groups = np.ascontiguousarray(groups, np.uint32)
+            n, gp = len(groups), _p(groups) if len(groups) else None
+        out = HeartbeatOutput()
+        self._check(lib.hq_worker_heartbeats(self.h, n, gp, ctypes.byref(out)),
+                    "hq_worker_heartbeats")
+        res = {"n_messages": out.n_messages, "gpu_ns": out.gpu_ns}
+        for name, count, dt in (("words", out.n_groups, np.dtype("<u4")),
+                                ("lags", out.n_lags, HEARTBEAT_LAG_DTYPE),
+                                ("ctxs", out.n_ctxs, HEARTBEAT_CTX_DTYPE)):
+            if count == 0:
+                res[name] = np.zeros(0, dt)
+                continue
+            buf = (ctypes.c_char * (count * dt.itemsize)).from_address(getattr(out, name))
+            res[name] = np.frombuffer(buf, dt).copy() if copy else np.frombuffer(buf, dt)
+        return res
+
 
 class StepJobs:
     """hq_worker_step_jobs over prepared jobs: jobs = [(worker, (groups, offsets, events))]
@@ -1940,6 +1993,54 @@ def encode_wire_batch(msgs, deployment_id=0, source_address=b"", out=None):
                                   len(source_address), _p(out), len(out), ctypes.byref(n)),
          "hq_wire_encode_batch")
     return out[:n.value]
+
+
+# ------------------------------------------------------------------------ leader heartbeats ----
+def heartbeats_expand(hb, cluster_id, term, committed, n_members, member_ids, cap=None):
+    """hq_heartbeats_expand: the reference's Heartbeat messages (HEARTBEAT_MSG_DTYPE; group
+    order, then member order) of a compact output `hb` (Worker.heartbeats' dict, or one built by
+    hand: 'words', 'lags', 'ctxs', 'n_messages'). The columns are per listed group; member_ids is
+    (n_groups, 16), the group's member ids in its add / set_group order. cap: the message buffer's
+    size (None: hb's n_messages); a short one raises HQError(HQ_E_STATE) whose `.n` is the count
+    needed."""
+    words = np.ascontiguousarray(hb["words"], np.uint32)
+    lags = np.ascontiguousarray(hb["lags"], HEARTBEAT_LAG_DTYPE)
+    ctxs = np.ascontiguousarray(hb["ctxs"], HEARTBEAT_CTX_DTYPE)
+    G = len(words)
+    cols = [np.ascontiguousarray(c, np.uint64) for c in (cluster_id, term, committed)]
+    nm = np.ascontiguousarray(n_members, np.uint32)
+    ids = np.ascontiguousarray(member_ids, np.uint64).reshape(-1)
+    assert all(len(c) == G for c in cols) and len(nm) == G and len(ids) == 16 * G
+    out = HeartbeatOutput(_p(words) if G else None, G, _p(lags) if len(lags) else None, len(lags),
+                          _p(ctxs) if len(ctxs) else None, len(ctxs), int(hb["n_messages"]), 0)
+    cap = int(hb["n_messages"]) if cap is None else cap
+    msgs = np.zeros(max(cap, 1), HEARTBEAT_MSG_DTYPE)
+    n = ctypes.c_uint64(0)
+    rc = lib.hq_heartbeats_expand(ctypes.byref(out), *[_p(c) if G else None for c in cols],
+                                  _p(nm) if G else None, _p(ids) if G else None, _p(msgs), cap,
+                                  ctypes.byref(n))
+    if rc != HQ_OK:
+        e = HQError(rc, "hq_heartbeats_expand: " + ("the messages do not fit cap" if rc == HQ_E_STATE
+                                                    else "inconsistent compact output"))
+        e.n = n.value
+        raise e
+    return msgs[:n.value]
+
+
+def heartbeat_wire_messages(msgs, frm):
+    """HEARTBEAT_MSG_DTYPE records as WIRE_MESSAGE_DTYPE rows of type Heartbeat from node `frm`
+    (a scalar or one id per message), ready for encode_wire_batch."""
+    m = np.zeros(len(msgs), WIRE_MESSAGE_DTYPE)
+    m["ev"]["kind"] = EV_MESSAGE
+    m["ev"]["type"] = HQ_MSG_HEARTBEAT
+    m["ev"]["from"] = frm
+    m["ev"]["term"] = msgs["term"]
+    m["ev"]["hint"] = msgs["hint"]
+    m["ev"]["hint_high"] = msgs["hint_high"]
+    m["cluster_id"] = msgs["cluster_id"]
+    m["to"] = msgs["to"]
+    m["commit"] = msgs["commit"]
+    return m
 
 
 class Wire:

@@ -1441,6 +1441,67 @@ int hq_wire_attach_device(hq_wire *w, hq_worker *worker);
 int hq_wire_step_device(hq_wire *w, hq_step_output *out, hq_wire_stats *stats);
 int hq_wire_device_rejected(hq_wire *w, const uint32_t **batches, uint64_t *n);
 
+/* ---------------------------------------------------------------- leader heartbeat broadcast -- */
+/*
+ * What a leader SENDS on a LeaderHeartbeat tick (handleLeaderHeartbeat, raft.go:1577-1579 ->
+ * broadcastHeartbeatMessage, raft.go:812-848), and after an accepted ReadIndex
+ * (handleLeaderReadIndex broadcasts with the new ctx, which is then readIndex.peepCtx,
+ * readindex.go:69-75): every voting member but the node itself gets
+ * Heartbeat{Commit: min(remote.match, log.committed), Hint: ctx}, ctx the LAST pending read's
+ * (peepCtx: the queue's tail) or zero when none is pending; observers get one only when ctx is
+ * zero. A device worker keeps remote.match, the committed index and the pending reads in HBM, so
+ * the answer is read there by two small kernels (hq_heartbeat.hip) and comes back compact: one
+ * word per listed group, a record per member that is behind, a record per group whose heartbeats
+ * carry a hint. The caller holds the rest (cluster ids, terms, member ids and the committed
+ * indices its commits told it), and hq_heartbeats_expand writes the messages. Additions to ABI 21
+ * (new symbols only); nothing of the step changes.
+ *
+ * The word of a listed group: bit i (0..15) — member i of the caller's members[] (add / set_group
+ * order) is sent a Heartbeat; bit 16 + i — that member's match < committed, so its Commit is its
+ * match (listed in `lags`), otherwise Commit = the group's committed index (match == committed is
+ * not behind). 0: nothing to send — not a leader, suspended (its events go to the CPU raft, which
+ * then sends its heartbeats), or no other member — and no record. Every index and ctx word is a
+ * full u64.
+ */
+#define HQ_MSG_HEARTBEAT 17u            /* raft.proto:44 */
+
+typedef struct hq_heartbeat_lag { uint32_t pos, member; uint64_t match; } hq_heartbeat_lag;
+typedef struct hq_heartbeat_ctx { uint64_t ctx_low, ctx_high; uint32_t pos, reserved; } hq_heartbeat_ctx;
+typedef struct hq_heartbeat_output {
+    const uint32_t *words;        uint64_t n_groups;
+    const hq_heartbeat_lag *lags; uint64_t n_lags;   /* group order, then member order */
+    const hq_heartbeat_ctx *ctxs; uint64_t n_ctxs;   /* groups whose heartbeats carry a hint */
+    uint64_t n_messages;          /* sum of popcount(word & 0xFFFF) */
+    uint64_t gpu_ns;              /* device workers: HIP-event time of the call's kernels */
+} hq_heartbeat_output;
+typedef struct hq_heartbeat_msg { uint64_t cluster_id, to, term, commit, hint, hint_high; } hq_heartbeat_msg;
+
+/* The heartbeats of the listed groups (worker handles; NULL: handles 0 .. n_groups - 1) in their
+ * state at the call — after every event of every earlier step — exactly as the reference
+ * handling pb.LeaderHeartbeat for each of them (raft.go:812-848, :1577-1579; ctx = peepCtx,
+ * readindex.go:69-75). Read-only: a handle may be listed more than once. Changes made with
+ * hq_worker_set_group / _add_group are uploaded first, as a step uploads them. A host worker
+ * computes the same output on the CPU. The arrays are owned by the worker and valid until its
+ * next hq_worker_heartbeats or close; they are not the step's buffers (the last hq_step_output
+ * stays valid). HQ_E_INVAL, with hq_worker_last_error set and nothing else done: a handle at or
+ * beyond the worker's group count, a group of more than 16 members (host workers only), a NULL
+ * out, n_groups >= 2^28. */
+int hq_worker_heartbeats(hq_worker *w, uint64_t n_groups, const uint32_t *groups, hq_heartbeat_output *out);
+
+/* Stateless, host only: the reference's Heartbeat messages (raft.go:812-848, sent from
+ * :1577-1579 with readindex.go:69-75's ctx) of a compact output, in group order, then member
+ * order. The columns are per listed group: cluster_id, term (finalizeMessageTerm,
+ * raft.go:650-652), committed, n_members, and member_ids (16 per group; the first n_members
+ * used). Commit = behind ? lag.match : committed[pos]; Hint / HintHigh from `ctxs`. *n = the
+ * messages (always set on HQ_OK and HQ_E_STATE); msgs[0 .. *n) written when they fit cap, else
+ * HQ_E_STATE and nothing written. HQ_E_INVAL for an inconsistent input: a behind bit outside the
+ * `to` mask, a bit at or beyond n_members (or n_members > 16), lags or ctxs out of order or for a
+ * position outside the list, a lag whose behind bit is not set, a ctx of a group with nothing to
+ * send or a zero ctx, counts (n_lags, n_messages) that do not match the words. */
+int hq_heartbeats_expand(const hq_heartbeat_output *hb, const uint64_t *cluster_id, const uint64_t *term,
+                         const uint64_t *committed, const uint32_t *n_members, const uint64_t *member_ids,
+                         hq_heartbeat_msg *msgs, uint64_t cap, uint64_t *n);
+
 /* ---------------------------------------------------------------- synthetic inputs ---------- */
 
 /*

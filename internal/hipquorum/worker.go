@@ -380,6 +380,89 @@ func (o *Output) EachReady(committedBefore func(i int) uint64, listedOf func(clu
 	}
 }
 
+// HeartbeatOutput is what the leaders among the listed groups send on a LeaderHeartbeat tick
+// (hq_worker_heartbeats: broadcastHeartbeatMessage, raft.go:812-848, sent from :1577-1579 with
+// readIndex.peepCtx, readindex.go:69-75), compact: one word per listed group, a record per member
+// that is behind the committed index, a record per group whose heartbeats carry a ctx. The arrays
+// live in the worker's buffers and are valid until its next Heartbeats call; the last step's
+// Output stays valid across the call.
+type HeartbeatOutput struct {
+	c C.hq_heartbeat_output
+}
+
+// Heartbeats computes the heartbeats of the listed groups (worker handles, repeats allowed; nil:
+// every handle 0 .. n-1 in order) in their state after every earlier step. It runs on the
+// heartbeat tick, and after a step for the groups that accepted a ReadIndex
+// (handleLeaderReadIndex broadcasts with the new ctx, which is then peepCtx). A device worker
+// reads its resident state with two small kernels; nothing of the state comes back but the
+// output.
+func (x *Worker) Heartbeats(groups []uint32, n int) (*HeartbeatOutput, error) {
+	o := &HeartbeatOutput{}
+	var gp *C.uint32_t
+	if groups != nil {
+		n = len(groups)
+		if n > 0 {
+			gp = (*C.uint32_t)(unsafe.Pointer(&groups[0]))
+		}
+	}
+	if rc := C.hq_worker_heartbeats(x.w, C.uint64_t(n), gp, &o.c); rc != C.HQ_OK {
+		return nil, x.err(rc)
+	}
+	return o, nil
+}
+
+// Messages is the number of Heartbeat messages the output stands for.
+func (o *HeartbeatOutput) Messages() uint64 { return uint64(o.c.n_messages) }
+
+// GPUNanos is the HIP-event time of the call's kernels (0 on a host worker).
+func (o *HeartbeatOutput) GPUNanos() uint64 { return uint64(o.c.gpu_ns) }
+
+// Each calls fn for every Heartbeat to send, in listed order, then member order: pos is the
+// group's place in the list and member the destination's place in the group's member list (its
+// AddGroup / SetGroup order). With commitIsMatch the message's Commit is match (the member is
+// behind, sendHeartbeatMessage's min(match, committed), raft.go:812-822); otherwise it is the
+// group's committed index, which the node holds. Term is the node's term
+// (finalizeMessageTerm, raft.go:650-652); Hint / HintHigh come from EachCtx.
+func (o *HeartbeatOutput) Each(fn func(pos int, member int, commitIsMatch bool, match uint64)) {
+	n := int(o.c.n_groups)
+	if n == 0 {
+		return
+	}
+	words := unsafe.Slice((*uint32)(unsafe.Pointer(o.c.words)), n)
+	var lags []C.hq_heartbeat_lag
+	if o.c.n_lags != 0 {
+		lags = unsafe.Slice(o.c.lags, int(o.c.n_lags))
+	}
+	k := 0
+	for pos, w := range words {
+		for m := 0; m < 16 && w&0xFFFF>>uint(m) != 0; m++ {
+			if w>>uint(m)&1 == 0 {
+				continue
+			}
+			if w>>uint(16+m)&1 != 0 {
+				var l C.hq_heartbeat_lag = lags[k]
+				k++
+				fn(pos, m, true, uint64(l.match))
+			} else {
+				fn(pos, m, false, 0)
+			}
+		}
+	}
+}
+
+// EachCtx calls fn(pos, ctx) for every listed group whose heartbeats carry a ReadIndex ctx (the
+// last pending read's, readindex.go:69-75), in listed order; every other group's carry the zero
+// ctx.
+func (o *HeartbeatOutput) EachCtx(fn func(pos int, ctx pb.SystemCtx)) {
+	if o.c.n_ctxs == 0 {
+		return
+	}
+	for _, r := range unsafe.Slice(o.c.ctxs, int(o.c.n_ctxs)) {
+		var c C.hq_heartbeat_ctx = r
+		fn(int(c.pos), pb.SystemCtx{Low: uint64(c.ctx_low), High: uint64(c.ctx_high)})
+	}
+}
+
 // StateChanges lists the step's leader / follower / candidate transitions.
 func (o *Output) StateChanges() []C.hq_state_change {
 	if o.c.n_state_changes == 0 {
