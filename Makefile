@@ -7,10 +7,12 @@ LIBDIR := dragonboat_amd/lib
 LIB := $(LIBDIR)/libhipquorum.so
 OBJS := $(LIBDIR)/hq_runtime.o $(LIBDIR)/hq_kernels.o $(LIBDIR)/hq_table.o $(LIBDIR)/hq_pack.o \
         $(LIBDIR)/hq_worker.o $(LIBDIR)/hq_wire.o $(LIBDIR)/hq_stream.o $(LIBDIR)/hq_jobs.o $(LIBDIR)/hq_dstep.o \
-        $(LIBDIR)/hq_engine.o $(LIBDIR)/hq_wire_frame.o $(LIBDIR)/hq_wire_dev.o $(LIBDIR)/hq_heartbeat.o
+        $(LIBDIR)/hq_engine.o $(LIBDIR)/hq_wire_frame.o $(LIBDIR)/hq_wire_dev.o $(LIBDIR)/hq_heartbeat.o \
+        $(LIBDIR)/hq_heartbeat_wire.o
 SRCS := $(CSRC)/hq_kernels.hip $(CSRC)/hq_table.hip $(CSRC)/hq_runtime.hip $(CSRC)/hq_pack.cpp \
         $(CSRC)/hq_worker.cpp $(CSRC)/hq_wire.cpp $(CSRC)/hq_stream.cpp $(CSRC)/hq_jobs.cpp $(CSRC)/hq_dstep.hip \
-        $(CSRC)/hq_engine.hip $(CSRC)/hq_wire_frame.cpp $(CSRC)/hq_wire_dev.hip $(CSRC)/hq_heartbeat.hip
+        $(CSRC)/hq_engine.hip $(CSRC)/hq_wire_frame.cpp $(CSRC)/hq_wire_dev.hip $(CSRC)/hq_heartbeat.hip \
+        $(CSRC)/hq_heartbeat_wire.hip
 DEPS := $(wildcard $(CSRC)/*.h) include/hipquorum.h
 CXX ?= g++
 CXXFLAGS ?= -O3 -std=c++17 -fPIC -pthread -Wall -Wextra

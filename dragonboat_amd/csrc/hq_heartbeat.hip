@@ -50,44 +50,10 @@ struct HbK {
     const uint64_t *n_messages;    // device: the Sum's result
 };
 
-// a member's fields the broadcast reads: match, and its position in the caller's list
-struct MemberRef {
-    uint64_t match;
-    uint32_t order;
-};
-
-__device__ inline MemberRef load_member(const hq_dmember *m) {
-    const uint64_t *p = reinterpret_cast<const uint64_t *>(m);
-    const uint64_t tail = p[2];                       // role, active, order, pad
-    return MemberRef{p[1], (uint32_t)(tail >> 16) & 0xFFu};
-}
-
-// the group's fields of the broadcast from its second and fourth 16 bytes
-struct GroupRef {
-    uint64_t committed;
-    uint32_t mem, n_members, n_voting, n_reads;
-    bool sends;                                       // a leader that is not suspended
-};
-
-__device__ inline GroupRef load_group(const hq_dgroup *g) {
-    const uint4 *p = reinterpret_cast<const uint4 *>(g);
-    const uint4 b = p[1], d = p[3];                   // term, committed | mem, 8 bytes, pad1
-    GroupRef r;
-    r.committed = (uint64_t)b.z | (uint64_t)b.w << 32;
-    r.mem = d.x;
-    r.n_members = d.y & 0xFFu;
-    r.n_voting = (d.y >> 8) & 0xFFu;
-    const uint32_t state = (d.y >> 16) & 0xFFu, flags = (d.z >> 8) & 0xFFu;
-    r.n_reads = (d.z >> 16) & 0xFFu;
-    r.sends = state == HQ_STATE_LEADER && !(flags & kDSuspended);
-    return r;
-}
-
-// the record checks both kernels rely on (the worker's own uploads satisfy them)
-__device__ inline bool group_ok(const HbK &k, const GroupRef &g) {
-    return g.n_members >= 1 && g.n_members <= kDMembers && g.n_voting <= g.n_members &&
-           g.n_reads <= kDReads && (uint64_t)g.mem + g.n_members <= k.n_state_members;
-}
+using hqhb::GroupRef;
+using hqhb::MemberRef;
+using hqhb::load_group;
+using hqhb::load_member;
 
 struct HbMessages {               // group i's messages
     const uint64_t *meta;
@@ -124,33 +90,11 @@ __global__ void __launch_bounds__(kBlock) k_hb_words(HbK k) {
     if (h >= k.n_state_groups) {
         atomicOr(k.error, kHbErrHandle);
     } else {
-        const GroupRef g = load_group(k.groups + h);
-        if (!group_ok(k, g)) {
-            atomicOr(k.error, kHbErrState);
-        } else if (g.sends) {
-            uint64_t lo = 0, hi = 0;                  // readIndex.peepCtx: the queue's tail
-            if (g.n_reads) {
-                const hq_dread *r = k.reads + h * kDReads + (g.n_reads - 1);
-                lo = r->low;
-                hi = r->high;
-            }
-            const bool zero_ctx = (lo | hi) == 0;
-            // pool order: the node, the other voting members, the observers (with a zero ctx)
-            const uint32_t end = zero_ctx ? g.n_members : g.n_voting;
-            const hq_dmember *m = k.members + g.mem;
-            bool bad = false;
-            for (uint32_t s = 1; s < end; ++s) {
-                const MemberRef r = load_member(m + s);
-                bad |= r.order >= kDMembers;
-                const uint32_t bit = 1u << (r.order & 15u);
-                word |= bit | (r.match < g.committed ? bit << 16 : 0u);
-            }
-            if (bad) {
-                atomicOr(k.error, kHbErrState);
-                word = 0;
-            }
-            has_ctx = word && !zero_ctx ? kHasCtx : 0;
-        }
+        uint32_t err = 0;
+        uint64_t lo = 0, hi = 0;
+        word = hqhb::word_of(k.groups, k.reads, k.members, k.n_state_members, h, &lo, &hi, &err);
+        if (err) atomicOr(k.error, err);
+        has_ctx = word && (lo | hi) ? kHasCtx : 0;
     }
     k.words[i] = word;
     k.meta[i] = word | has_ctx;

@@ -28,6 +28,7 @@
 #include "../../include/hipquorum.h"
 #include "hq_dstep.h"
 #include "hq_heartbeat.h"
+#include "hq_heartbeat_wire.h"
 
 namespace {
 
@@ -106,6 +107,15 @@ struct hq_worker {
     std::vector<uint32_t> hb_words;       // host worker: its heartbeat output
     std::vector<hq_heartbeat_lag> hb_lags;
     std::vector<hq_heartbeat_ctx> hb_ctxs;
+    // hq_worker_heartbeat_batches: the route column (16 words per group; rows [lo, hi) not yet on
+    // the device), a device worker's buffers (first call), a host worker's output
+    std::vector<uint16_t> routes;
+    uint64_t routes_lo = 0, routes_hi = 0, routes_on_dev = 0;   // (rows the device column holds)
+    hq_hbw_dev *hbw = nullptr;
+    std::vector<uint8_t> hbw_bytes;
+    std::vector<hq_heartbeat_batch> hbw_batches;
+    std::vector<hb_fields> hbw_msgs;
+    std::vector<uint64_t> hbw_first;
     std::vector<hq_event> decoded;        // host worker: a stream step's rows
     std::vector<uint64_t> sized_off, sized_boff;   // host worker: a sized stream's prefixes
     std::vector<uint32_t> sized_groups;            // and its implicit handles
@@ -175,6 +185,8 @@ struct hq_worker {
     int load_group(Group &g, const hq_worker_group *src, const hq_member *m, bool fresh);
     int step(const hq_step_input *in, hq_step_output *out);
     int heartbeats(uint64_t n, const uint32_t *list, hq_heartbeat_output *out);
+    int heartbeat_batches(uint64_t n, const uint32_t *list, const hq_heartbeat_wire_config *cfg,
+                          hq_heartbeat_batches *out);
     Verdict handle(Group &g, const hq_event &e, uint64_t ei);
     Verdict read_index(Group &g, uint64_t from, uint64_t low, uint64_t high, uint64_t ei);
     void advance(Group &g);
@@ -1027,8 +1039,175 @@ int hq_worker::heartbeats(uint64_t n, const uint32_t *list, hq_heartbeat_output 
     return HQ_OK;
 }
 
+// The same heartbeats as MessageBatch bytes, one run of batches per destination. A device worker's
+// are marshalled where the state lives (hq_heartbeat_wire.hip); a host worker's here, with the same
+// marshaller (hq_heartbeat_wire.h), into the same output.
+int hq_worker::heartbeat_batches(uint64_t n, const uint32_t *list, const hq_heartbeat_wire_config *cfg,
+                                 hq_heartbeat_batches *out) {
+    const char *const bad_route = "hq_worker_heartbeat_batches: a route at or above n_dest";
+    routes.resize(groups.size() * kDMembers, (uint16_t)HQ_ROUTE_NONE);
+    if (dstep) {
+        int rc = sync_to_device();
+        if (rc) return rc;
+        if (!hbw && (rc = hq(hq_hbw_dev_open(ctx, &hbw), "hq_worker_heartbeat_batches"))) return rc;
+        if (routes_on_dev < groups.size()) {            // rows of groups added since
+            routes_lo = routes_lo == routes_hi ? routes_on_dev : std::min(routes_lo, routes_on_dev);
+            routes_hi = groups.size();
+        }
+        rc = hq(hq_hbw_dev_put_routes(hbw, routes.data(), groups.size(), routes_lo, routes_hi),
+                "hq_worker_heartbeat_batches");
+        if (rc) return rc;
+        routes_lo = routes_hi = 0;
+        routes_on_dev = groups.size();
+        if (n == 0) {
+            std::memset(out, 0, sizeof *out);
+            return HQ_OK;
+        }
+        hq_dstate_view st;
+        hq_dstep_view(dstep, &st);
+        uint32_t e = 0;
+        hq_heartbeat_batches res;
+        rc = hq_hbw_dev_run(hbw, &st, dev_members, n, list, cfg, &res, &e);
+        if (rc == HQ_E_INVAL && e)
+            return e & kHbErrHandle
+                       ? fail(HQ_E_INVAL, "hq_worker_heartbeat_batches: unknown group handle")
+                       : e & kHbErrState
+                             ? fail(HQ_E_STATE, "hq_worker_heartbeat_batches: a resident group record "
+                                                "is out of range (internal)")
+                             : fail(HQ_E_INVAL, bad_route);
+        if (!rc) *out = res;
+        return hq(rc, "hq_worker_heartbeat_batches");
+    }
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint64_t h = list ? list[i] : i;
+        if (h >= groups.size())
+            return fail(HQ_E_INVAL, "hq_worker_heartbeat_batches: unknown group handle");
+        if (groups[h].n_members > kDMembers)
+            return fail(HQ_E_INVAL, "hq_worker_heartbeat_batches: a group of more than 16 members");
+        for (uint32_t o = 0; o < groups[h].n_members; ++o) {
+            const uint16_t r = routes[h * kDMembers + o];
+            if (r != HQ_ROUTE_NONE && r >= cfg->n_dest) return fail(HQ_E_INVAL, bad_route);
+        }
+    }
+    // two passes over the list: the destinations' message counts, then the messages at their
+    // places (listed order, then member order within a destination)
+    uint64_t unrouted = 0, total = 0;
+    hbw_first.assign((size_t)cfg->n_dest + 1, 0);
+    for (int write = 0; write < 2; ++write) {
+        for (uint64_t i = 0; i < n; ++i) {
+            const uint64_t h = list ? list[i] : i;
+            const Group &g = groups[h];
+            if (g.state != HQ_STATE_LEADER || g.has(kSuspended)) continue;
+            const ReadQueue *q = g.rq == kNone ? nullptr : &rqs[g.rq];
+            uint64_t lo = 0, hi = 0;                    // readIndex.peepCtx: the queue's tail
+            if (q && q->n) {
+                lo = q->r[q->n - 1].low;
+                hi = q->r[q->n - 1].high;
+            }
+            const Member *m = pool.data() + g.mem;
+            const uint32_t end = (lo | hi) == 0 ? g.n_members : g.n_voting;
+            const Member *by_order[kDMembers] = {};
+            for (uint32_t s = 1; s < end; ++s) by_order[m[s].order] = m + s;
+            for (uint32_t o = 0; o < kDMembers; ++o) {
+                if (!by_order[o]) continue;
+                const uint16_t r = routes[h * kDMembers + o];
+                if (r == HQ_ROUTE_NONE) {
+                    unrouted += !write;
+                } else if (!write) {
+                    ++hbw_first[r + 1];
+                } else {
+                    hbw_msgs[hbw_first[r]++] =
+                        hb_fields{by_order[o]->node_id, g.node_id, g.cluster_id, g.term,
+                                  std::min(by_order[o]->match, g.committed), lo, hi};
+                }
+            }
+        }
+        if (!write) {
+            for (uint32_t d = 0; d < cfg->n_dest; ++d) hbw_first[d + 1] += hbw_first[d];
+            total = hbw_first[cfg->n_dest];
+            hbw_msgs.resize(total);
+        }
+    }
+    // (hbw_first[d] is now destination d's end)
+    const uint64_t bm = cfg->batch_messages ? cfg->batch_messages : UINT64_MAX;
+    const uint32_t trailer = hb_trailer_size(cfg->deployment_id, cfg->source_len);
+    hbw_batches.clear();
+    uint64_t bytes = 0, j = 0;
+    for (uint32_t d = 0; d < cfg->n_dest; ++d) {
+        for (const uint64_t end = hbw_first[d]; j < end;) {
+            const uint64_t cnt = std::min(bm, end - j);
+            uint64_t len = trailer;
+            for (uint64_t x = j; x < j + cnt; ++x) len += hb_msg_size(hbw_msgs[x]);
+            hbw_batches.push_back({bytes, len, d, (uint32_t)cnt});
+            bytes += len;
+            j += cnt;
+        }
+    }
+    hbw_bytes.resize(bytes);
+    j = 0;
+    for (const hq_heartbeat_batch &b : hbw_batches) {
+        uint8_t *p = hbw_bytes.data() + b.offset;
+        for (uint32_t x = 0; x < b.n_messages; ++x) p = hb_msg_put(p, hbw_msgs[j++]);
+        hb_trailer_put(p, cfg->deployment_id, cfg->source, cfg->source_len);
+    }
+    std::memset(out, 0, sizeof *out);
+    out->bytes = hbw_bytes.data();
+    out->n_bytes = bytes;
+    out->batches = hbw_batches.data();
+    out->n_batches = hbw_batches.size();
+    out->n_messages = total;
+    out->n_unrouted = unrouted;
+    return HQ_OK;
+}
+
 // ------------------------------------------------------------------------------ C-ABI ------
 extern "C" {
+
+int hq_worker_set_heartbeat_routes(hq_worker *w, uint32_t first_handle, uint64_t n_groups,
+                                   const uint16_t *routes) {
+    if (!w) return HQ_E_INVAL;
+    try {
+        if (n_groups && !routes)
+            return w->fail(HQ_E_INVAL, "hq_worker_set_heartbeat_routes: routes is NULL");
+        if (first_handle > w->groups.size() || n_groups > w->groups.size() - first_handle)
+            return w->fail(HQ_E_INVAL, "hq_worker_set_heartbeat_routes: unknown group handle");
+        if (!n_groups) return HQ_OK;
+        w->routes.resize(w->groups.size() * kDMembers, (uint16_t)HQ_ROUTE_NONE);
+        std::memcpy(w->routes.data() + (size_t)first_handle * kDMembers, routes,
+                    n_groups * kDMembers * sizeof(uint16_t));
+        const uint64_t lo = first_handle, hi = first_handle + n_groups;
+        if (w->routes_lo == w->routes_hi) {
+            w->routes_lo = lo;
+            w->routes_hi = hi;
+        } else {
+            w->routes_lo = std::min(w->routes_lo, lo);
+            w->routes_hi = std::max(w->routes_hi, hi);
+        }
+        return HQ_OK;
+    } catch (const std::bad_alloc &) {
+        return w->fail(HQ_E_NOMEM, "hq_worker_set_heartbeat_routes: out of memory");
+    }
+}
+
+int hq_worker_heartbeat_batches(hq_worker *w, uint64_t n_groups, const uint32_t *groups,
+                                const hq_heartbeat_wire_config *cfg, hq_heartbeat_batches *out) {
+    if (!w) return HQ_E_INVAL;
+    try {
+        if (!cfg || !out) return w->fail(HQ_E_INVAL, "hq_worker_heartbeat_batches: cfg or out is NULL");
+        if (cfg->n_dest < 1 || cfg->n_dest > 65535)
+            return w->fail(HQ_E_INVAL, "hq_worker_heartbeat_batches: n_dest must be 1 .. 65535");
+        if (cfg->source_len > kHbSourceMax || (cfg->source_len && !cfg->source))
+            return w->fail(HQ_E_INVAL, "hq_worker_heartbeat_batches: a source of more than 256 bytes "
+                                       "(or NULL)");
+        if (n_groups >= (uint64_t(1) << 28))
+            return w->fail(HQ_E_INVAL, "hq_worker_heartbeat_batches: 2^28 or more groups in one call");
+        if (!groups && n_groups > w->groups.size())
+            return w->fail(HQ_E_INVAL, "hq_worker_heartbeat_batches: unknown group handle");
+        return w->heartbeat_batches(n_groups, groups, cfg, out);
+    } catch (const std::bad_alloc &) {
+        return w->fail(HQ_E_NOMEM, "hq_worker_heartbeat_batches: out of memory");
+    }
+}
 
 int hq_worker_heartbeats(hq_worker *w, uint64_t n_groups, const uint32_t *groups,
                          hq_heartbeat_output *out) {
@@ -1133,6 +1312,7 @@ int hq_worker_open_ex(int device, uint32_t n_max, uint32_t flags, hq_worker **ou
 void hq_worker_close(hq_worker *w) {
     if (!w) return;
     if (w->hb) hq_hb_dev_close(w->hb);
+    if (w->hbw) hq_hbw_dev_close(w->hbw);
     if (w->dstep) hq_dstep_close(w->dstep);
     if (w->ctx) {
         hq_sync(w->ctx);

@@ -214,6 +214,27 @@ class HeartbeatOutput(ctypes.Structure):
                 ("n_messages", ctypes.c_uint64), ("gpu_ns", ctypes.c_uint64)]
 
 
+# leader heartbeats as MessageBatch bytes (hq_worker_set_heartbeat_routes / _heartbeat_batches)
+HQ_ROUTE_NONE = 0xFFFF
+HEARTBEAT_BATCH_DTYPE = np.dtype([("offset", "<u8"), ("len", "<u8"), ("dest", "<u4"),
+                                  ("n_messages", "<u4")], align=True)
+
+
+class HeartbeatWireConfig(ctypes.Structure):
+    """Mirror of ``hq_heartbeat_wire_config``."""
+
+    _fields_ = [("deployment_id", ctypes.c_uint64), ("source", _vp), ("source_len", ctypes.c_uint32),
+                ("n_dest", ctypes.c_uint32), ("batch_messages", ctypes.c_uint32)]
+
+
+class HeartbeatBatches(ctypes.Structure):
+    """Mirror of ``hq_heartbeat_batches``."""
+
+    _fields_ = [("bytes", _vp), ("n_bytes", ctypes.c_uint64), ("batches", _vp),
+                ("n_batches", ctypes.c_uint64), ("n_messages", ctypes.c_uint64),
+                ("n_unrouted", ctypes.c_uint64), ("gpu_ns", ctypes.c_uint64)]
+
+
 class WireBatchInfo(ctypes.Structure):
     _fields_ = [("n_messages", ctypes.c_uint64), ("deployment_id", ctypes.c_uint64),
                 ("source_address_len", ctypes.c_uint64), ("bin_ver", ctypes.c_uint32),
@@ -474,6 +495,10 @@ SIGNATURES = {
     "hq_worker_group_count": (ctypes.c_int, [_vp, _u64p]),
     "hq_worker_heartbeats": (ctypes.c_int, [_vp, ctypes.c_uint64, _vp,
                                             ctypes.POINTER(HeartbeatOutput)]),
+    "hq_worker_set_heartbeat_routes": (ctypes.c_int, [_vp, ctypes.c_uint32, ctypes.c_uint64, _vp]),
+    "hq_worker_heartbeat_batches": (ctypes.c_int, [_vp, ctypes.c_uint64, _vp,
+                                                   ctypes.POINTER(HeartbeatWireConfig),
+                                                   ctypes.POINTER(HeartbeatBatches)]),
     "hq_heartbeats_expand": (ctypes.c_int, [ctypes.POINTER(HeartbeatOutput), _vp, _vp, _vp, _vp,
                                             _vp, _vp, ctypes.c_uint64, _u64p]),
     "hq_synth_commit_dev": (ctypes.c_int, [_vp, ctypes.POINTER(SynthSpec), ctypes.POINTER(CommitArgs)]),
@@ -1630,6 +1655,47 @@ class Worker:
         for name, count, dt in (("words", out.n_groups, np.dtype("<u4")),
                                 ("lags", out.n_lags, HEARTBEAT_LAG_DTYPE),
                                 ("ctxs", out.n_ctxs, HEARTBEAT_CTX_DTYPE)):
+            if count == 0:
+                res[name] = np.zeros(0, dt)
+                continue
+            buf = (ctypes.c_char * (count * dt.itemsize)).from_address(getattr(out, name))
+            res[name] = np.frombuffer(buf, dt).copy() if copy else np.frombuffer(buf, dt)
+        return res
+
+    def set_heartbeat_routes(self, first_handle, routes):
+        """hq_worker_set_heartbeat_routes: `routes` is (n_groups, 16) uint16, row g the routes of
+        handle first_handle + g: word i the destination index of member i of the group's member
+        list, HQ_ROUTE_NONE for none."""
+        routes = np.ascontiguousarray(routes, np.uint16)
+        if routes.ndim != 2 or routes.shape[1] != 16:
+            raise ValueError("routes must be (n_groups, 16)")
+        self._check(lib.hq_worker_set_heartbeat_routes(self.h, first_handle, len(routes),
+                                                       _p(routes) if len(routes) else None),
+                    "hq_worker_set_heartbeat_routes")
+
+    def heartbeat_batches(self, groups=None, deployment_id=0, source=b"", n_dest=1,
+                          batch_messages=0, copy=True):
+        """hq_worker_heartbeat_batches: the heartbeats of `groups` (as heartbeats takes them) as
+        MessageBatch bytes per destination. Returns a dict: 'bytes' (uint8), 'batches'
+        (HEARTBEAT_BATCH_DTYPE: batch b is bytes[offset : offset + len], for destination dest),
+        'n_messages', 'n_unrouted', 'gpu_ns'. With copy=False the arrays are views of the worker's
+        buffers, valid until its next heartbeat_batches call."""
+        if groups is None:
+            n, gp = self.group_count(), None
+        else:
+            groups = np.ascontiguousarray(groups, np.uint32)
+            n, gp = len(groups), _p(groups) if len(groups) else None
+        source = bytes(source)
+        src = ctypes.create_string_buffer(source, max(len(source), 1))
+        cfg = HeartbeatWireConfig(deployment_id, ctypes.cast(src, _vp), len(source), n_dest,
+                                  batch_messages)
+        out = HeartbeatBatches()
+        self._check(lib.hq_worker_heartbeat_batches(self.h, n, gp, ctypes.byref(cfg),
+                                                    ctypes.byref(out)),
+                    "hq_worker_heartbeat_batches")
+        res = {"n_messages": out.n_messages, "n_unrouted": out.n_unrouted, "gpu_ns": out.gpu_ns}
+        for name, count, dt in (("bytes", out.n_bytes, np.dtype("u1")),
+                                ("batches", out.n_batches, HEARTBEAT_BATCH_DTYPE)):
             if count == 0:
                 res[name] = np.zeros(0, dt)
                 continue

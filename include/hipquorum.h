@@ -1502,6 +1502,65 @@ int hq_heartbeats_expand(const hq_heartbeat_output *hb, const uint64_t *cluster_
                          const uint64_t *committed, const uint32_t *n_members, const uint64_t *member_ids,
                          hq_heartbeat_msg *msgs, uint64_t cap, uint64_t *n);
 
+/* ------------------------------------------------- leader heartbeats as MessageBatch bytes -- */
+/*
+ * The sending twin of the wire's device mode: the Heartbeat messages of hq_worker_heartbeats
+ * marshalled where the state lives, as complete MessageBatch byte strings, one run of batches per
+ * destination host, which the transport sends as they are. The worker is told once where each
+ * member lives (the route column); a device worker (hq_heartbeat_wire.hip) then writes the bytes
+ * straight into pinned host memory and the host touches no message. A host worker computes the
+ * same output on the CPU. Additions to ABI 21 (new symbols only); read-only on the group state.
+ *
+ * The messages are exactly those of hq_worker_heartbeats over the same list in the same state:
+ * Type 17, To = the member's node id, From = the group's node id, ClusterId, Term = the group's
+ * term (finalizeMessageTerm, raft.go:650-652), LogTerm = LogIndex = Reject = 0, Commit =
+ * min(match, committed), Hint / HintHigh = the read queue's tail ctx or 0. The message of member
+ * i of listed position pos goes to destination routes[handle][i]; with HQ_ROUTE_NONE it is left
+ * out and counted in n_unrouted. Within a destination the order is listed order, then member
+ * order; a handle listed twice contributes twice. Every batch bytes[offset .. offset + len) is
+ * what hq_wire_encode_batch writes for its messages with deployment_id and source; a destination
+ * with no message has no batch. A marshalled Heartbeat is 50 .. 113 bytes.
+ */
+#define HQ_ROUTE_NONE 0xFFFFu   /* no destination: the member's heartbeat is not marshalled */
+
+/* routes of groups [first_handle, first_handle + n_groups): 16 words per group, word i = the
+ * destination index of member i of the caller's members[] (add / set_group order, the order
+ * hq_heartbeat_output's bits use). Kept by the worker until set again; a group never set has
+ * HQ_ROUTE_NONE everywhere. Device workers keep them in a device column of their own, uploaded
+ * with the pending set_group changes by the next hq_worker_heartbeat_batches. HQ_E_INVAL: a
+ * handle at or beyond the worker's group count, NULL routes. */
+int hq_worker_set_heartbeat_routes(hq_worker *w, uint32_t first_handle, uint64_t n_groups,
+                                   const uint16_t *routes);
+
+typedef struct hq_heartbeat_wire_config {
+    uint64_t deployment_id;
+    const uint8_t *source; uint32_t source_len;   /* source_address, <= 256 bytes */
+    uint32_t n_dest;                              /* routes are < n_dest; 1 .. 65535 */
+    uint32_t batch_messages;                      /* 0: one batch per destination; else a batch
+                                                     is cut after every batch_messages messages */
+} hq_heartbeat_wire_config;
+
+typedef struct hq_heartbeat_batch { uint64_t offset, len; uint32_t dest, n_messages; } hq_heartbeat_batch;
+typedef struct hq_heartbeat_batches {
+    const uint8_t *bytes; uint64_t n_bytes;       /* pinned host memory, owned by the worker
+                                                     (a host worker's: plain host memory) */
+    const hq_heartbeat_batch *batches; uint64_t n_batches;   /* by dest, then in sequence */
+    uint64_t n_messages, n_unrouted, gpu_ns;
+} hq_heartbeat_batches;
+
+/* The heartbeats of the listed groups (as hq_worker_heartbeats lists them) as MessageBatch bytes.
+ * The batches are contiguous from offset 0 in table order. The arrays are valid until the
+ * worker's next hq_worker_heartbeat_batches or close; the last hq_step_output and the last
+ * hq_heartbeat_output stay valid. A list with nothing to send gives HQ_OK and zero batches.
+ * HQ_E_INVAL, with hq_worker_last_error set and nothing else done: a NULL cfg or out, n_dest 0 or
+ * above 65535, source_len above 256 (or a NULL source with a length), n_groups >= 2^28, a bad
+ * handle, a group of more than 16 members (host workers only), or a route >= n_dest that is not
+ * HQ_ROUTE_NONE among the routes of a listed group's members (whatever the group sends now; the
+ * words at and beyond its member count are not read). HQ_E_NOMEM: out of memory. The worker stays
+ * usable. */
+int hq_worker_heartbeat_batches(hq_worker *w, uint64_t n_groups, const uint32_t *groups,
+                                const hq_heartbeat_wire_config *cfg, hq_heartbeat_batches *out);
+
 /* ---------------------------------------------------------------- synthetic inputs ---------- */
 
 /*

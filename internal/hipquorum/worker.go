@@ -463,6 +463,97 @@ func (o *HeartbeatOutput) EachCtx(fn func(pos int, ctx pb.SystemCtx)) {
 	}
 }
 
+// RouteNone is HQ_ROUTE_NONE: the member has no destination and its heartbeat is not marshalled.
+const RouteNone = uint16(0xFFFF)
+
+// SetHeartbeatRoutes tells the worker where the members of groups [firstHandle, firstHandle +
+// len(routes)/16) live: 16 words per group, word i the destination index of member i of the
+// group's member list (its AddGroup / SetGroup order), RouteNone for none. The worker keeps the
+// routes until they are set again; a device worker uploads them with the next HeartbeatBatches.
+func (x *Worker) SetHeartbeatRoutes(firstHandle uint32, routes []uint16) error {
+	if len(routes)%16 != 0 {
+		return fmt.Errorf("hipquorum: SetHeartbeatRoutes: %d route words, not 16 per group", len(routes))
+	}
+	if len(routes) == 0 {
+		return nil
+	}
+	rc := C.hq_worker_set_heartbeat_routes(x.w, C.uint32_t(firstHandle), C.uint64_t(len(routes)/16),
+		(*C.uint16_t)(unsafe.Pointer(&routes[0])))
+	if rc != C.HQ_OK {
+		return x.err(rc)
+	}
+	return nil
+}
+
+// HeartbeatBatch is one marshalled MessageBatch of a HeartbeatBatches call: Bytes is a view of the
+// worker's buffer (pinned host memory on a device worker), not a copy, ready for the transport to
+// send to destination Dest as it is.
+type HeartbeatBatch struct {
+	Dest     uint32
+	Messages uint32
+	Bytes    []byte
+}
+
+// HeartbeatBatchOutput is the result of HeartbeatBatches. The batches are ordered by destination,
+// then in sequence, and are valid until the worker's next HeartbeatBatches call or Close.
+type HeartbeatBatchOutput struct {
+	c       C.hq_heartbeat_batches
+	Batches []HeartbeatBatch
+}
+
+// Messages is the number of Heartbeat messages marshalled, Unrouted the number left out because
+// their member's route is RouteNone, Bytes the size of all batches, GPUNanos the HIP-event time of
+// the call's kernels (0 on a host worker).
+func (o *HeartbeatBatchOutput) Messages() uint64 { return uint64(o.c.n_messages) }
+func (o *HeartbeatBatchOutput) Unrouted() uint64 { return uint64(o.c.n_unrouted) }
+func (o *HeartbeatBatchOutput) Bytes() uint64    { return uint64(o.c.n_bytes) }
+func (o *HeartbeatBatchOutput) GPUNanos() uint64 { return uint64(o.c.gpu_ns) }
+
+// HeartbeatBatches marshals the heartbeats of the listed groups (as Heartbeats lists them) into
+// complete MessageBatch byte strings, one run of batches per destination of SetHeartbeatRoutes
+// (hq_worker_heartbeat_batches). deploymentID and source are the batch's DeploymentId and
+// SourceAddress; nDest is the number of destinations; a batch is cut after every batchMessages
+// messages (0: one batch per destination), which the caller chooses so that 113 * batchMessages
+// plus the trailer stays under its batch limit (settings.MaxMessageBatchSize,
+// transport.go:460-472). A device worker writes the bytes on the GPU; the host touches no message.
+func (x *Worker) HeartbeatBatches(groups []uint32, n int, deploymentID uint64, source string,
+	nDest uint32, batchMessages uint32) (*HeartbeatBatchOutput, error) {
+	o := &HeartbeatBatchOutput{}
+	var gp *C.uint32_t
+	if groups != nil {
+		n = len(groups)
+		if n > 0 {
+			gp = (*C.uint32_t)(unsafe.Pointer(&groups[0]))
+		}
+	}
+	src := []byte(source)
+	var cfg C.hq_heartbeat_wire_config
+	cfg.deployment_id = C.uint64_t(deploymentID)
+	cfg.n_dest = C.uint32_t(nDest)
+	cfg.batch_messages = C.uint32_t(batchMessages)
+	cfg.source_len = C.uint32_t(len(src))
+	if len(src) > 0 {
+		// (C memory: the struct passed to C may not hold a Go pointer)
+		cfg.source = (*C.uint8_t)(C.CBytes(src))
+		defer C.free(unsafe.Pointer(cfg.source))
+	}
+	if rc := C.hq_worker_heartbeat_batches(x.w, C.uint64_t(n), gp, &cfg, &o.c); rc != C.HQ_OK {
+		return nil, x.err(rc)
+	}
+	if o.c.n_batches == 0 {
+		return o, nil
+	}
+	all := unsafe.Slice((*byte)(unsafe.Pointer(o.c.bytes)), int(o.c.n_bytes))
+	table := unsafe.Slice(o.c.batches, int(o.c.n_batches))
+	o.Batches = make([]HeartbeatBatch, len(table))
+	for i := range table {
+		var b C.hq_heartbeat_batch = table[i]
+		o.Batches[i] = HeartbeatBatch{Dest: uint32(b.dest), Messages: uint32(b.n_messages),
+			Bytes: all[b.offset : b.offset+b.len : b.offset+b.len]}
+	}
+	return o, nil
+}
+
 // StateChanges lists the step's leader / follower / candidate transitions.
 func (o *Output) StateChanges() []C.hq_state_change {
 	if o.c.n_state_changes == 0 {
