@@ -2328,19 +2328,13 @@ int restore(Run &r, int code) {
     return code ? code : r2;
 }
 
-// the device's address of host memory it can read (pinned by hipHostMalloc / registered), or
-// NULL (pageable memory: copied instead)
+// hq::device_view of a step input, which is host memory: pinned memory only (anything else is
+// copied instead)
 template <class T>
 const T *pinned_on_device(const T *p) {
-    hipPointerAttribute_t at;
-    if (!p || hipPointerGetAttributes(&at, p) != hipSuccess) {
-        (void)hipGetLastError();  // pageable host memory reports an error: clear it
-        return nullptr;
-    }
-    if (at.type != hipMemoryTypeHost || !at.devicePointer) return nullptr;
-    const char *hp = static_cast<const char *>(at.hostPointer ? at.hostPointer : (const void *)p);
-    return reinterpret_cast<const T *>(static_cast<const char *>(at.devicePointer) +
-                                       (reinterpret_cast<const char *>(p) - hp));
+    bool pinned;
+    const void *d = hq::device_view(p, &pinned);
+    return pinned ? static_cast<const T *>(d) : nullptr;
 }
 
 // HQ_STEP_JOBS_SPIN_US: how long the jobs path's one waiting thread polls before it waits as the

@@ -2,7 +2,7 @@
 // (hq_worker_heartbeat_batches, include/hipquorum.h "leader heartbeats as MessageBatch bytes"):
 // the messages of hq_worker_heartbeats, routed to destination hosts by the worker's route column
 // and written as complete MessageBatch byte strings, one run of batches per destination, straight
-// into pinned host memory. The sending twin of hq_wire_dev.hip. Read-only on the resident state.
+// into pinned host memory. The sending side of hq_wire_dev.hip. Read-only on the resident state.
 //
 // On the context's stream behind the last step:
 //   k_hbw_words   one lane per listed group: its word (hqhb::word_of, as k_hb_words), its route

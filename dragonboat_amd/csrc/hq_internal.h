@@ -57,6 +57,10 @@ int check_hip(hq_ctx *ctx, hipError_t e, const char *what);
 int pre_launch(hq_ctx *ctx);
 int post_launch(hq_ctx *ctx, const char *what);
 int ensure_workspace(hq_ctx *ctx, size_t bytes);
+// where the device reads p: device memory as it is, host memory it can read (pinned by
+// hipHostMalloc / registered; *pinned set) where it is mapped, NULL for anything else (pageable
+// memory: copied instead)
+const void *device_view(const void *p, bool *pinned = nullptr);
 
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 inline uint64_t words64(uint64_t G) { return (G + 63) / 64; }

@@ -59,6 +59,20 @@ int ensure_workspace(hq_ctx *ctx, size_t bytes) {
     return HQ_OK;
 }
 
+const void *device_view(const void *p, bool *pinned) {
+    if (pinned) *pinned = false;
+    hipPointerAttribute_t at;
+    if (!p || hipPointerGetAttributes(&at, p) != hipSuccess) {
+        (void)hipGetLastError();  // pageable host memory reports an error: clear it
+        return nullptr;
+    }
+    if (at.type == hipMemoryTypeDevice) return p;
+    if (at.type != hipMemoryTypeHost || !at.devicePointer) return nullptr;
+    if (pinned) *pinned = true;
+    const char *hp = static_cast<const char *>(at.hostPointer ? at.hostPointer : p);
+    return static_cast<const char *>(at.devicePointer) + (static_cast<const char *>(p) - hp);
+}
+
 }  // namespace hq
 
 extern "C" {

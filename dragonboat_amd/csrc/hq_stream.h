@@ -19,6 +19,23 @@ struct WireEvent {
 };
 static_assert(sizeof(WireEvent) == 56, "56-byte wire records");
 
+// the step's row of a wire event (host, and the device wire's row kernel)
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline hq_event to_event(const WireEvent &r) {
+    hq_event e{};
+    e.kind = r.kind;
+    e.type = r.type;
+    e.from = r.from;
+    e.term = r.term;
+    e.log_index = r.log_index;
+    e.hint = r.hint;
+    e.hint_high = r.hint_high;
+    e.reject = r.reject;
+    return e;
+}
+
 // one group's events ev[0 .. n) encoded at p as hq_events_encode does (its runs and repeat
 // codes); NULL when fewer than HQ_EVENT_STREAM_MAX bytes are left before an event
 uint8_t *encode_group(uint8_t *p, const uint8_t *end, const hq_event *ev, uint64_t n);

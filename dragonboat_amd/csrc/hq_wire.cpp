@@ -12,7 +12,6 @@
 // (Message.MarshalTo raft.pb.go:2232-2300, MessageBatch.MarshalTo :2417-2445); the decoder
 // accepts any valid proto2 encoding of them (fields in any order, unknown fields skipped, as
 // Message.Unmarshal raft.pb.go:4831 / raft_optimized.go:654 do).
-#include <cstring>
 #include <new>
 #include <string>
 #include <utility>
@@ -20,189 +19,62 @@
 
 #include "../../include/hipquorum.h"
 #include "hq_stream.h"
+#include "hq_wire_codec.h"
 #include "hq_wire_dev.h"
 
 namespace {
 
-constexpr uint32_t kSnapshotReceived = 22;   // raft.proto MessageType
+using hqw::kSnapshotReceived;
 
-struct Reader {
-    const uint8_t *p, *end;
-    const char *err = nullptr;
-
-    bool varint(uint64_t &v) {
-        if (p < end && *p < 0x80) {                   // the common one-byte varint
-            v = *p++;
-            return true;
-        }
-        v = 0;
-        for (int shift = 0; shift < 64; shift += 7) {
-            if (p >= end) {
-                err = "unexpected end of data in a varint";
-                return false;
-            }
-            const uint8_t b = *p++;
-            v |= (uint64_t)(b & 0x7F) << shift;
-            if (b < 0x80) return true;
-        }
-        err = "varint overflows 64 bits";
-        return false;
+// why hqw::decode_message rejected a message, in words
+std::string message_error(const hqw::error &e) {
+    switch (e.code) {
+    case hqw::kVarintEnd: return "Message: unexpected end of data in a varint";
+    case hqw::kVarintOverflow: return "Message: varint overflows 64 bits";
+    case hqw::kFieldZero: return "Message: illegal field number 0";
+    case hqw::kWrongType:
+        return "Message: wrong wire type " + std::to_string(e.wt) + " for field " +
+               std::to_string(e.field);
+    case hqw::kGroup: return "Message: unsupported wire type (groups are not part of raft.proto)";
+    case hqw::kFieldEnd: return "Message: unexpected end of data in a field";
+    case hqw::kBytesEnd: return "Message: unexpected end of data in a length-delimited field";
     }
-    // skip a field of the given wire type (skipRaft, raft.pb.go:6293)
-    bool skip(uint32_t wt) {
-        uint64_t n = 0;
-        switch (wt) {
-        case 0: return varint(n);
-        case 1: n = 8; break;
-        case 2:
-            if (!varint(n)) return false;
-            break;
-        case 5: n = 4; break;
-        default:
-            err = "unsupported wire type (groups are not part of raft.proto)";
-            return false;
-        }
-        if ((uint64_t)(end - p) < n) {
-            err = "unexpected end of data in a field";
-            return false;
-        }
-        p += n;
-        return true;
-    }
-    bool bytes(const uint8_t *&b, uint64_t &n) {
-        if (!varint(n)) return false;
-        if ((uint64_t)(end - p) < n) {
-            err = "unexpected end of data in a length-delimited field";
-            return false;
-        }
-        b = p;
-        p += n;
-        return true;
-    }
-};
-
-// raftpb.Message (raft.proto:154-168) into the fields the quorum path reads
-int decode_message(const uint8_t *b, size_t len, hq_wire_message *m, std::string &err) {
-    std::memset(m, 0, sizeof(*m));
-    m->ev.kind = HQ_EV_MESSAGE;
-    Reader r{b, b + len};
-    while (r.p < r.end) {
-        uint64_t tag;
-        if (!r.varint(tag)) break;
-        const uint32_t field = (uint32_t)(tag >> 3), wt = (uint32_t)(tag & 7);
-        if (field == 0) {
-            r.err = "illegal field number 0";
-            break;
-        }
-        uint64_t v = 0;
-        if (field <= 10 || field == 13) {              // the varint fields
-            if (wt != 0) {
-                err = "Message: wrong wire type " + std::to_string(wt) + " for field " +
-                      std::to_string(field);
-                return HQ_E_INVAL;
-            }
-            if (!r.varint(v)) break;
-        }
-        switch (field) {
-        case 1: m->ev.type = (uint32_t)v; break;      // type
-        case 2: m->to = v; break;
-        case 3: m->ev.from = v; break;
-        case 4: m->cluster_id = v; break;
-        case 5: m->ev.term = v; break;
-        case 6: m->log_term = v; break;
-        case 7: m->ev.log_index = v; break;
-        case 8: m->commit = v; break;
-        case 9: m->ev.reject = v != 0; break;
-        case 10: m->ev.hint = v; break;
-        case 13: m->ev.hint_high = v; break;
-        case 11:                                       // repeated Entry entries
-        case 12: {                                     // Snapshot snapshot
-            if (wt != 2) {
-                err = "Message: wrong wire type " + std::to_string(wt) + " for field " +
-                      std::to_string(field);
-                return HQ_E_INVAL;
-            }
-            const uint8_t *x;
-            uint64_t n;
-            if (!r.bytes(x, n)) break;
-            if (field == 11) m->n_entries++;
-            else m->has_snapshot = 1;
-            break;
-        }
-        default:
-            r.skip(wt);
-        }
-        if (r.err) break;
-    }
-    if (r.err) {
-        err = std::string("Message: ") + r.err;
-        return HQ_E_INVAL;
-    }
-    return HQ_OK;
+    return std::string();
 }
 
 // one event of the step as the wire keeps it (hq_stream.h): a decoded message's fields, or a
 // local event's
-struct Rec : hqs::WireEvent {
-    hq_event event() const {
-        hq_event e{};
-        e.kind = kind;
-        e.type = type;
-        e.from = from;
-        e.term = term;
-        e.log_index = log_index;
-        e.hint = hint;
-        e.hint_high = hint_high;
-        e.reject = reject;
-        return e;
-    }
-};
-static_assert(sizeof(Rec) == 56, "56-byte wire records");
-
-// the one-byte varint, else the loop; p < end on entry
-inline bool varint_at(const uint8_t *&p, const uint8_t *end, uint64_t &v) {
-    if (*p < 0x80) {
-        v = *p++;
-        return true;
-    }
-    v = 0;
-    for (int shift = 0; shift < 64; shift += 7) {
-        if (p >= end) return false;
-        const uint8_t b = *p++;
-        v |= (uint64_t)(b & 0x7F) << shift;
-        if (b < 0x80) return true;
-    }
-    return false;
-}
+using Rec = hqs::WireEvent;
 
 // A Message in the field order raft.pb.go Message.MarshalTo writes (:2232-2296): every field of
 // 1-10 with its tag in order, entries (11) repeated, the snapshot (12, always: nullable=false),
 // hint_high (13), nothing else. false: not that layout (the general decoder takes it from the
 // start, any field order); *entries counts field 11
-inline bool decode_marshal_order(const uint8_t *p, const uint8_t *end, Rec &r, uint64_t &cluster,
+inline bool decode_marshal_order(const uint8_t *b, size_t end, Rec &r, uint64_t &cluster,
                                  uint32_t &entries) {
+    size_t p = 0;
     uint64_t v[10];
     // fields 1-10: tag (f + 1) << 3, a varint — unrolled, so that each field's tag is a constant
     // and each field's varint length has a branch of its own to predict (the lengths differ by
     // field and repeat from message to message)
 #pragma GCC unroll 10
     for (uint32_t f = 0; f < 10; ++f) {
-        if (p >= end || *p != (uint8_t)((f + 1) << 3)) return false;
-        if (++p >= end || !varint_at(p, end, v[f])) return false;
+        if (p >= end || b[p] != (uint8_t)((f + 1) << 3)) return false;
+        if (++p >= end || !hqw::varint(b, p, end, v[f])) return false;
     }
     entries = 0;
-    while (p < end && *p == 0x5a) {                // entries: counted, not decoded
+    while (p < end && b[p] == 0x5a) {              // entries: counted, not decoded
         uint64_t n;
-        if (++p >= end || !varint_at(p, end, n) || (uint64_t)(end - p) < n) return false;
+        if (++p >= end || !hqw::varint(b, p, end, n) || (uint64_t)(end - p) < n) return false;
         p += n;
         ++entries;
     }
     uint64_t n, high;
-    if (p >= end || *p != 0x62) return false;      // the snapshot
-    if (++p >= end || !varint_at(p, end, n) || (uint64_t)(end - p) < n) return false;
+    if (p >= end || b[p] != 0x62) return false;    // the snapshot
+    if (++p >= end || !hqw::varint(b, p, end, n) || (uint64_t)(end - p) < n) return false;
     p += n;
-    if (p >= end || *p != 0x68) return false;      // hint_high, the last field
-    if (++p >= end || !varint_at(p, end, high) || p != end) return false;
+    if (p >= end || b[p] != 0x68) return false;    // hint_high, the last field
+    if (++p >= end || !hqw::varint(b, p, end, high) || p != end) return false;
     r.kind = HQ_EV_MESSAGE;
     r.type = (uint32_t)v[0];
     r.from = v[2];
@@ -213,65 +85,6 @@ inline bool decode_marshal_order(const uint8_t *p, const uint8_t *end, Rec &r, u
     r.hint = v[9];
     r.hint_high = high;
     return true;
-}
-
-// MessageBatch (raft.proto:191-196): every Message handed to sink(bytes, len) in order (sink
-// returns an HQ_ status), the other fields into *bi. Any field order; unknown fields skipped.
-template <class Sink>
-int parse_batch(const uint8_t *bytes, size_t len, hq_wire_batch_info *bi, uint64_t *count,
-                Sink &&sink) {
-    *bi = hq_wire_batch_info{};
-    *count = 0;
-    Reader r{bytes, bytes + len};
-    while (r.p < r.end) {
-        // the common case first: a Message (tag 0x0a) shorter than 128 bytes
-        if (r.end - r.p >= 2 && r.p[0] == 0x0a && r.p[1] < 0x80) {
-            const uint64_t n = r.p[1];
-            if ((uint64_t)(r.end - r.p - 2) < n) {
-                r.err = "unexpected end of data in a length-delimited field";
-                break;
-            }
-            const uint8_t *m = r.p + 2;
-            r.p = m + n;
-            const int rc = sink(m, (size_t)n);
-            if (rc) return rc;
-            ++*count;
-            continue;
-        }
-        uint64_t tag;
-        if (!r.varint(tag)) break;
-        const uint32_t field = (uint32_t)(tag >> 3), wt = (uint32_t)(tag & 7);
-        if (field == 1 && wt == 2) {                  // repeated Message requests
-            const uint8_t *m;
-            uint64_t n;
-            if (!r.bytes(m, n)) break;
-            const int rc = sink(m, (size_t)n);
-            if (rc) return rc;
-            ++*count;
-        } else if (field == 2 && wt == 0) {           // deployment_id
-            if (!r.varint(bi->deployment_id)) break;
-        } else if (field == 3 && wt == 2) {           // source_address
-            const uint8_t *a;
-            uint64_t n;
-            if (!r.bytes(a, n)) break;
-            bi->source_address_len = n;
-        } else if (field == 4 && wt == 0) {           // bin_ver
-            uint64_t v;
-            if (!r.varint(v)) break;
-            bi->bin_ver = (uint32_t)v;
-        } else if (field == 0) {
-            r.err = "illegal field number 0";
-            break;
-        } else if (field <= 4) {
-            r.err = "wrong wire type for a MessageBatch field";
-            break;
-        } else if (!r.skip(wt)) {
-            break;
-        }
-    }
-    if (r.err) return HQ_E_INVAL;
-    bi->n_messages = *count;
-    return HQ_OK;
 }
 
 // cluster id -> index in order of first appearance: open addressing, linear probing (a step
@@ -285,19 +98,7 @@ class ClusterIndex {
     }
     // the value of id, or false
     bool find(uint64_t id, uint32_t *v) const {
-        if (id == kEmpty) {
-            if (has_empty_) *v = empty_val_;
-            return has_empty_;
-        }
-        if (slots_.empty()) return false;
-        const uint64_t mask = slots_.size() - 1;
-        for (uint64_t i = hash(id) & mask;; i = (i + 1) & mask) {
-            if (slots_[i].key == id) {
-                *v = slots_[i].val;
-                return true;
-            }
-            if (slots_[i].key == kEmpty) return false;
-        }
+        return hqw::find(slots_.data(), slots_.size(), has_empty_, empty_val_, id, *v);
     }
     void prefetch(uint64_t id) const {
         if (!slots_.empty()) __builtin_prefetch(&slots_[hash(id) & (slots_.size() - 1)]);
@@ -332,17 +133,9 @@ class ClusterIndex {
         }
     }
   private:
-    static constexpr uint64_t kEmpty = ~0ull;
-    static uint64_t hash(uint64_t x) {
-        x ^= x >> 33;
-        x *= 0xff51afd7ed558ccdull;
-        return x ^ (x >> 33);
-    }
-    // key and value side by side: a lookup touches one 16-byte slot
-    struct Slot {
-        uint64_t key;
-        uint32_t val, pad;
-    };
+    using Slot = hqw::Slot;
+    static constexpr uint64_t kEmpty = hqw::kEmptyKey;
+    static uint64_t hash(uint64_t x) { return hqw::hash_id(x); }
     void rehash(size_t cap) {
         std::vector<Slot> k(cap, Slot{kEmpty, 0, 0});
         std::vector<uint32_t> u;
@@ -464,15 +257,17 @@ extern "C" {
 int hq_wire_decode_batch(const uint8_t *bytes, size_t len, hq_wire_message *out, uint64_t cap,
                          uint64_t *count, hq_wire_batch_info *info) {
     if ((!bytes && len) || !count) return HQ_E_INVAL;
-    std::string err;
     hq_wire_batch_info bi;
-    uint64_t k = 0;
-    const int rc = parse_batch(bytes, len, &bi, count, [&](const uint8_t *m, size_t n) {
-        hq_wire_message tmp;
-        hq_wire_message *dst = out && k < cap ? out + k : &tmp;
-        ++k;
-        return decode_message(m, n, dst, err);
-    });
+    const int rc = hqw::walk_batch(
+        bytes, len, bi,
+        [&](size_t, size_t body, size_t n) {
+            hq_wire_message tmp;
+            hqw::error e;
+            hq_wire_message &dst = out && bi.n_messages < cap ? out[bi.n_messages] : tmp;
+            return hqw::decode_message(bytes + body, n, dst, e) ? HQ_OK : HQ_E_INVAL;
+        },
+        [] {});
+    *count = bi.n_messages;
     if (rc) return rc;
     if (info) *info = bi;
     return *count > cap && out ? HQ_E_STATE : HQ_OK;
@@ -485,55 +280,21 @@ int hq_wire_encode_batch(const hq_wire_message *msgs, uint64_t n, uint64_t deplo
                          const uint8_t *source, size_t source_len, uint8_t *out, uint64_t cap,
                          uint64_t *len) {
     if ((n && !msgs) || !len || (source_len && !source) || (cap && !out)) return HQ_E_INVAL;
-    static const uint8_t kSnap[24] = {0x12, 0, 0x18, 0, 0x20, 0, 0x28, 0, 0x32, 2, 0x08, 0,
-                                      0x48, 0, 0x50, 0, 0x58, 0, 0x60, 0, 0x68, 0, 0x70, 0};
-    auto vlen = [](uint64_t v) {
-        uint32_t k = 1;
-        while (v >= 0x80) {
-            v >>= 7;
-            ++k;
-        }
-        return k;
-    };
-    auto put = [](uint8_t *p, uint64_t v) {
-        while (v >= 0x80) {
-            *p++ = (uint8_t)(v | 0x80);
-            v >>= 7;
-        }
-        *p++ = (uint8_t)v;
-        return p;
-    };
     uint8_t *p = out, *const end = out + cap;
     for (uint64_t i = 0; i < n; ++i) {
         const hq_wire_message &m = msgs[i];
         if (m.n_entries) return HQ_E_INVAL;      // (entries are not marshalled here)
-        const uint64_t f[10] = {m.ev.type, m.to, m.ev.from, m.cluster_id, m.ev.term, m.log_term,
-                                m.ev.log_index, m.commit, m.ev.reject ? 1u : 0u, m.ev.hint};
-        uint64_t size = 2 + sizeof kSnap + 1 + vlen(m.ev.hint_high);
-        for (uint64_t v : f) size += 1 + vlen(v);
-        if ((uint64_t)(end - p) < size + 1 + vlen(size)) return HQ_E_STATE;
-        *p++ = 0x0a;                              // requests (1), length-delimited
-        p = put(p, size);
-        for (uint32_t k = 0; k < 10; ++k) {
-            *p++ = (uint8_t)((k + 1) << 3);
-            p = put(p, f[k]);
-        }
-        *p++ = 0x62;
-        *p++ = (uint8_t)sizeof kSnap;
-        std::memcpy(p, kSnap, sizeof kSnap);
-        p += sizeof kSnap;
-        *p++ = 0x68;
-        p = put(p, m.ev.hint_high);
+        const uint64_t reject = m.ev.reject ? 1u : 0u;
+        const uint64_t size = hqw::body_size(m.ev.type, m.to, m.ev.from, m.cluster_id, m.ev.term,
+                                             m.log_term, m.ev.log_index, m.commit, reject, m.ev.hint,
+                                             m.ev.hint_high);
+        if ((uint64_t)(end - p) < size + 1 + hqw::vlen(size)) return HQ_E_STATE;
+        p = hqw::put_field(p, 0x0a, size);        // requests (1), length-delimited
+        p = hqw::put_body(p, m.ev.type, m.to, m.ev.from, m.cluster_id, m.ev.term, m.log_term,
+                          m.ev.log_index, m.commit, reject, m.ev.hint, m.ev.hint_high);
     }
     if ((uint64_t)(end - p) < 1 + 10 + 1 + 10 + source_len + 1 + 10) return HQ_E_STATE;
-    *p++ = 0x10;                                  // deployment_id (2)
-    p = put(p, deployment_id);
-    *p++ = 0x1a;                                  // source_address (3)
-    p = put(p, source_len);
-    if (source_len) std::memcpy(p, source, source_len);
-    p += source_len;
-    *p++ = 0x20;                                  // bin_ver (4)
-    p = put(p, HQ_RPC_BIN_VERSION);
+    p = hqw::put_trailer(p, deployment_id, source, source_len);
     *len = (uint64_t)(p - out);
     return HQ_OK;
 }
@@ -711,20 +472,19 @@ int hq_wire_add_batch(hq_wire *w, const uint8_t *bytes, size_t len) {
             ++no_cluster;
         }
     };
-    std::string err;
+    hqw::error err{};
     hq_wire_batch_info bi;
-    uint64_t n = 0;
-    const int rc = parse_batch(bytes, len, &bi, &n, [&](const uint8_t *m, size_t k) {
+    auto on_message = [&](size_t, size_t body, size_t k) {
+        const uint8_t *const m = bytes + body;
         Rec r;
         r.key = 0;
         r.pad = 0;
         r.pad2 = 0;
         uint64_t cid;
         uint32_t ent;
-        if (!decode_marshal_order(m, m + k, r, cid, ent)) {
+        if (!decode_marshal_order(m, k, r, cid, ent)) {
             hq_wire_message x;
-            const int e = decode_message(m, k, &x, err);
-            if (e) return e;
+            if (!hqw::decode_message(m, k, x, err)) return HQ_E_INVAL;
             r.kind = HQ_EV_MESSAGE;
             r.type = x.ev.type;
             r.from = x.ev.from;
@@ -750,7 +510,9 @@ int hq_wire_add_batch(hq_wire *w, const uint8_t *bytes, size_t len) {
             if (w->pending.size() - looked > kAhead) look_up();
         }
         return HQ_OK;
-    });
+    };
+    const int rc = hqw::walk_batch(bytes, len, bi, on_message, [] {});
+    const uint64_t n = bi.n_messages;
     if (now) {
         while (looked < w->pending.size()) look_up();
         if (no_cluster && !rc) {       // the records of clusters the worker does not run leave
@@ -763,7 +525,7 @@ int hq_wire_add_batch(hq_wire *w, const uint8_t *bytes, size_t len) {
     if (rc) {
         w->drop_from(r0);
         return w->fail(HQ_E_INVAL, "hq_wire_add_batch: malformed MessageBatch" +
-                                       (err.empty() ? std::string() : ": " + err));
+                                       (err.code ? ": " + message_error(err) : std::string()));
     }
     w->stats.batches++;
     w->stats.bytes += len;
@@ -812,7 +574,7 @@ int hq_wire_step_input(hq_wire *w, hq_worker *worker, hq_step_input *out, hq_wir
         }
         if (b == e) continue;
         w->groups.push_back(handle[k]);
-        for (uint64_t j = b; j < e; ++j) w->events.push_back(w->recs[perm[j]].event());
+        for (uint64_t j = b; j < e; ++j) w->events.push_back(hqs::to_event(w->recs[perm[j]]));
         w->offsets.push_back(w->events.size());
     }
     out->n_groups = w->groups.size();

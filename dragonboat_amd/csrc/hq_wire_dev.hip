@@ -1,13 +1,8 @@
 // hq_wire_dev.hip — raftpb.Message decode on the device (include/hipquorum.h "wire decode on the
 // device"): the spans hq_wire_frame_batch (hq_wire_frame.cpp) cut out of MessageBatch bytes,
-// decoded into hq_wire_message records, one wave per span and one lane per message.
-//
-// The decoder is the device twin of hq_wire.cpp's decode_message and keeps its treatment of odd
-// but accepted input (any field order, a repeated scalar takes its last value, the tag's field
-// number truncated to 32 bits, unknown fields skipped by wire type). The bytes come from the
-// network: every loop consumes at least one byte of a message per iteration, a varint reads at
-// most 10 bytes, and no byte outside a span is read. The kernel waits on nothing but its own
-// workgroup's two barriers.
+// decoded into hq_wire_message records, one wave per span and one lane per message. The reader is
+// hq_wire_codec.h's, the one the host decodes with. No byte outside a span is read, and the kernel
+// waits on nothing but its own workgroup's two barriers.
 //
 // The device mode of hq_wire (hq_wire_attach_device) follows in the same file: the decoded records
 // keyed by the worker's handle through a device hash table, sorted with the step's local events by
@@ -21,11 +16,14 @@
 
 #include "hq_dstep.h"
 #include "hq_internal.h"
+#include "hq_wire_codec.h"
 #include "hq_wire_dev.h"
 
 namespace {
 
-constexpr uint32_t kSnapshotReceived = 22;   // raft.proto MessageType
+using hqw::kEmptyKey;
+using hqw::kSnapshotReceived;
+using hqw::Slot;
 
 constexpr uint32_t kThreads = 256, kWaves = kThreads / 64;   // a wave per span
 
@@ -38,92 +36,6 @@ struct WaveStage {
     uint32_t framed;                          // the headers are where the span says
     uint32_t pad[3];
 };
-
-// p < end on entry is not required; I is the position type (32 bits in LDS, 64 in memory)
-template <class I>
-__host__ __device__ __forceinline__ bool varint(const uint8_t *b, I &p, I end, uint64_t &v) {
-    v = 0;
-#pragma unroll 1
-    for (int shift = 0; shift < 64; shift += 7) {
-        if (p >= end) return false;               // unexpected end of data in a varint
-        const uint8_t x = b[p++];
-        v |= (uint64_t)(x & 0x7F) << shift;
-        if (x < 0x80) return true;
-    }
-    return false;                                 // varint overflows 64 bits
-}
-
-// the `requests` header at p: its body's position and length; false when it is not one, or runs
-// past end
-template <class I>
-__host__ __device__ __forceinline__ bool header(const uint8_t *b, I &p, I end, uint64_t &n) {
-    uint64_t tag;
-    if (!varint(b, p, end, tag)) return false;
-    if ((uint32_t)(tag >> 3) != 1 || (uint32_t)(tag & 7) != 2) return false;
-    if (!varint(b, p, end, n)) return false;
-    return (uint64_t)(end - p) >= n;
-}
-
-// decode_message (hq_wire.cpp:84-141) over b[0 .. end); false: rejected
-template <class I>
-__host__ __device__ bool decode_message(const uint8_t *b, I end, hq_wire_message &m) {
-    m = hq_wire_message{};
-    m.ev.kind = HQ_EV_MESSAGE;
-    I p = 0;
-    while (p < end) {
-        uint64_t tag;
-        if (!varint(b, p, end, tag)) return false;
-        const uint32_t field = (uint32_t)(tag >> 3), wt = (uint32_t)(tag & 7);
-        if (field == 0) return false;
-        uint64_t v = 0;
-        if (field <= 10 || field == 13) {             // the varint fields
-            if (wt != 0) return false;
-            if (!varint(b, p, end, v)) return false;
-        }
-        switch (field) {
-        case 1: m.ev.type = (uint32_t)v; break;
-        case 2: m.to = v; break;
-        case 3: m.ev.from = v; break;
-        case 4: m.cluster_id = v; break;
-        case 5: m.ev.term = v; break;
-        case 6: m.log_term = v; break;
-        case 7: m.ev.log_index = v; break;
-        case 8: m.commit = v; break;
-        case 9: m.ev.reject = v != 0; break;
-        case 10: m.ev.hint = v; break;
-        case 13: m.ev.hint_high = v; break;
-        case 11:                                   // entries: counted and skipped
-        case 12: {                                 // the snapshot: noted and skipped
-            if (wt != 2) return false;
-            uint64_t n;
-            if (!varint(b, p, end, n)) return false;
-            if ((uint64_t)(end - p) < n) return false;
-            p += (I)n;
-            if (field == 11) m.n_entries++;
-            else m.has_snapshot = 1;
-            break;
-        }
-        default: {                                 // unknown: skipped by wire type
-            uint64_t n = 0;
-            switch (wt) {
-            case 0:
-                if (!varint(b, p, end, n)) return false;
-                n = 0;
-                break;
-            case 1: n = 8; break;
-            case 2:
-                if (!varint(b, p, end, n)) return false;
-                break;
-            case 5: n = 4; break;
-            default: return false;                 // groups are not part of raft.proto
-            }
-            if ((uint64_t)(end - p) < n) return false;
-            p += (I)n;
-        }
-        }
-    }
-    return true;
-}
 
 // the decode kernel's arguments; REC (the device mode): the records go out as the wire's 56-byte
 // events with their batch in `key` and their entry count in `pad2`, the cluster ids aside, and a
@@ -185,7 +97,7 @@ __global__ void __launch_bounds__(kThreads) k_wire_decode(const DecodeK a) {
         uint32_t p = 0, k = 0;
         for (; k < count; ++k) {
             uint64_t n;
-            if (!header<uint32_t>(b, p, L, n)) break;
+            if (!hqw::header<uint32_t>(b, p, L, n)) break;
             st.pos[k] = p;
             st.len[k] = (uint32_t)n;
             p += (uint32_t)n;
@@ -199,12 +111,13 @@ __global__ void __launch_bounds__(kThreads) k_wire_decode(const DecodeK a) {
     if (i >= a.n_messages) return;
     bool ok = false;
     hq_wire_message m;
+    hqw::error why;                                   // (the host's to put in words; unused here)
     if (valid && !large) {
-        if (st.framed) ok = decode_message<uint32_t>(sb + sh + st.pos[lane], st.len[lane], m);
+        if (st.framed) ok = hqw::decode_message<uint32_t>(sb + sh + st.pos[lane], st.len[lane], m, why);
     } else if (valid) {                               // one message, one lane, from memory
         uint64_t p = 0, n;
-        if (header<uint64_t>(g, p, sp.len, n) && p + n == sp.len)
-            ok = decode_message<uint64_t>(g + p, n, m);
+        if (hqw::header<uint64_t>(g, p, sp.len, n) && p + n == sp.len)
+            ok = hqw::decode_message<uint64_t>(g + p, n, m, why);
     }
     if (REC) {
         const uint32_t batch = a.span_batch[s];
@@ -233,18 +146,6 @@ __global__ void __launch_bounds__(kThreads) k_wire_decode(const DecodeK a) {
 }
 
 // ---- the device mode: keys, sort, rows ----
-
-struct Slot {                                         // the handle table: hq_wire.cpp ClusterIndex's
-    uint64_t key;
-    uint32_t val, pad;
-};
-constexpr uint64_t kEmptyKey = ~0ull;                 // the one key the table cannot hold
-
-__host__ __device__ inline uint64_t hash_id(uint64_t x) {
-    x ^= x >> 33;
-    x *= 0xff51afd7ed558ccdull;
-    return x ^ (x >> 33);
-}
 
 struct KeysK {
     const hqs::WireEvent *recs;
@@ -281,26 +182,8 @@ __global__ void __launch_bounds__(256) k_wire_keys(const KeysK a) {
             if (r.type == kSnapshotReceived) {
                 c[2] = 1;
             } else {
-                const uint64_t id = a.cids[i];
-                bool found = false;
                 uint32_t h = 0;
-                if (id == kEmptyKey) {
-                    found = a.has_empty != 0;
-                    h = a.empty_val;
-                } else {
-                    const uint64_t mask = a.n_slots - 1;
-                    uint64_t s = hash_id(id) & mask;
-                    for (uint64_t probe = 0; probe < a.n_slots; ++probe, s = (s + 1) & mask) {
-                        const uint64_t k = a.slots[s].key;
-                        if (k == id) {
-                            found = true;
-                            h = a.slots[s].val;
-                            break;
-                        }
-                        if (k == kEmptyKey) break;
-                    }
-                }
-                if (found) key = h * 4 + 1;
+                if (hqw::find(a.slots, a.n_slots, a.has_empty, a.empty_val, a.cids[i], h)) key = h * 4 + 1;
                 else c[3] = 1;
             }
         }
@@ -334,17 +217,7 @@ __global__ void __launch_bounds__(256) k_wire_rows(const hqs::WireEvent *recs, c
                                                    const uint64_t *n_rows, hq_event *events) {
     const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (j >= *n_rows) return;
-    const hqs::WireEvent r = recs[vals[j]];
-    hq_event e{};
-    e.kind = r.kind;
-    e.type = r.type;
-    e.from = r.from;
-    e.term = r.term;
-    e.log_index = r.log_index;
-    e.hint = r.hint;
-    e.hint_high = r.hint_high;
-    e.reject = r.reject;
-    events[j] = e;
+    events[j] = hqs::to_event(recs[vals[j]]);
 }
 
 struct DevBuf {
@@ -428,18 +301,19 @@ struct hq_wire_dev {
         if (!rc) b.cap = want;
         return rc;
     }
+    // an id's first handle stays
     void insert(uint64_t id, uint32_t h) {
+        uint32_t first;
+        if (hqw::find(slots.data(), slots.size(), has_empty, empty_val, id, first)) return;
         if (id == kEmptyKey) {
-            if (!has_empty) {
-                has_empty = true;
-                empty_val = h;
-            }
+            has_empty = true;
+            empty_val = h;
             return;
         }
         const uint64_t mask = slots.size() - 1;
-        uint64_t s = hash_id(id) & mask;
-        while (slots[s].key != kEmptyKey && slots[s].key != id) s = (s + 1) & mask;
-        if (slots[s].key == kEmptyKey) slots[s] = Slot{id, h, 0};
+        uint64_t s = hqw::hash_id(id) & mask;
+        while (slots[s].key != kEmptyKey) s = (s + 1) & mask;
+        slots[s] = Slot{id, h, 0};
     }
     // the table holds every group of the worker (load <= 1/2); uploaded when it has changed
     int extend(uint64_t G) {
@@ -463,24 +337,6 @@ struct hq_wire_dev {
         return rc;
     }
 };
-
-namespace {
-
-// where the device reads host-visible memory (pinned or device memory), or NULL
-const uint8_t *device_view(const uint8_t *p) {
-    hipPointerAttribute_t at;
-    if (!p || hipPointerGetAttributes(&at, p) != hipSuccess) {
-        (void)hipGetLastError();                      // pageable memory reports an error: clear it
-        return nullptr;
-    }
-    if (at.type == hipMemoryTypeDevice) return p;
-    if (at.type != hipMemoryTypeHost || !at.devicePointer) return nullptr;
-    const char *hp = static_cast<const char *>(at.hostPointer ? at.hostPointer : (const void *)p);
-    return reinterpret_cast<const uint8_t *>(static_cast<const char *>(at.devicePointer) +
-                                             (reinterpret_cast<const char *>(p) - hp));
-}
-
-}  // namespace
 
 int hq_wire_dev_open(hq_worker *worker, hq_wire_dev **out) {
     hq_ctx *ctx = hq_worker_device_ctx(worker);
@@ -532,7 +388,8 @@ int hq_wire_dev_add_batch(hq_wire_dev *d, const uint8_t *bytes, size_t len, cons
         return d->fail(HQ_E_STATE, "hq_wire_add_batch: a device step holds < 2^31 messages");
     int rc = d->hip(hipSetDevice(d->ctx->device), "hipSetDevice");
     if (rc) return rc;
-    const uint8_t *dev = device_view(bytes);
+    // device memory as it is, pinned memory where the device maps it
+    const uint8_t *dev = static_cast<const uint8_t *>(hq::device_view(bytes));
     if (!dev) {                                       // any other memory: into the pinned staging
         StageBlock *blk = nullptr;
         for (StageBlock &s : d->stage)

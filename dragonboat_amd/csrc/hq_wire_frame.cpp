@@ -1,48 +1,11 @@
 // hq_wire_frame.cpp — the host's share of the device wire decode: a raftpb.MessageBatch framed
-// into spans (include/hipquorum.h "wire decode on the device"). Plain C++; no HIP, no worker.
-//
-// The walk is hq_wire.cpp's parse_batch (MessageBatch, raft.proto:191-196: any field order,
-// unknown fields skipped, the same framing errors), but a `requests` field is only hopped over:
-// its tag, its length and nothing of its body are read. What is inside a message is the decode
-// kernel's business (hq_wire_dev.hip).
+// into spans (include/hipquorum.h "wire decode on the device"). Plain C++; no HIP, no worker. The
+// batch is walked by hqw::walk_batch (hq_wire_codec.h); a `requests` field is only hopped over:
+// what is inside a message is the decode kernel's business (hq_wire_dev.hip).
 #include "../../include/hipquorum.h"
+#include "hq_wire_codec.h"
 
 namespace {
-
-struct Reader {
-    const uint8_t *p, *end;
-
-    bool varint(uint64_t &v) {
-        v = 0;
-        for (int shift = 0; shift < 64; shift += 7) {
-            if (p >= end) return false;              // unexpected end of data in a varint
-            const uint8_t b = *p++;
-            v |= (uint64_t)(b & 0x7F) << shift;
-            if (b < 0x80) return true;
-        }
-        return false;                                // varint overflows 64 bits
-    }
-    // a length-delimited field's body hopped over
-    bool bytes(uint64_t &n) {
-        if (!varint(n)) return false;
-        if ((uint64_t)(end - p) < n) return false;
-        p += n;
-        return true;
-    }
-    bool skip(uint32_t wt) {
-        uint64_t n = 0;
-        switch (wt) {
-        case 0: return varint(n);
-        case 1: n = 8; break;
-        case 2: return bytes(n);
-        case 5: n = 4; break;
-        default: return false;                       // groups are not part of raft.proto
-        }
-        if ((uint64_t)(end - p) < n) return false;
-        p += n;
-        return true;
-    }
-};
 
 // the spans as they are formed: counted always, written while they fit
 struct Spans {
@@ -82,42 +45,18 @@ extern "C" int hq_wire_frame_batch(const uint8_t *bytes, size_t len, uint64_t ba
                                    hq_wire_batch_info *info) {
     if ((!bytes && len) || !n_spans) return HQ_E_INVAL;
     *n_spans = 0;
-    hq_wire_batch_info bi{};
+    hq_wire_batch_info bi;
     Spans s{spans, cap};
-    uint64_t count = 0;
-    Reader r{bytes, bytes + len};
-    while (r.p < r.end) {
-        const uint8_t *const f0 = r.p;
-        uint64_t tag;
-        if (!r.varint(tag)) return HQ_E_INVAL;
-        const uint32_t field = (uint32_t)(tag >> 3), wt = (uint32_t)(tag & 7);
-        if (field == 1 && wt == 2) {                  // repeated Message requests
-            uint64_t n;
-            if (!r.bytes(n)) return HQ_E_INVAL;
-            if (count >= UINT32_MAX) return HQ_E_INVAL;   // (a span's `first` is 32 bits)
-            s.add(base + (uint64_t)(f0 - bytes), (uint64_t)(r.p - f0), (uint32_t)count);
-            ++count;
-            continue;
-        }
-        s.close();                                    // a span is `requests` fields back to back
-        if (field == 2 && wt == 0) {                  // deployment_id
-            if (!r.varint(bi.deployment_id)) return HQ_E_INVAL;
-        } else if (field == 3 && wt == 2) {           // source_address
-            uint64_t n;
-            if (!r.bytes(n)) return HQ_E_INVAL;
-            bi.source_address_len = n;
-        } else if (field == 4 && wt == 0) {           // bin_ver
-            uint64_t v;
-            if (!r.varint(v)) return HQ_E_INVAL;
-            bi.bin_ver = (uint32_t)v;
-        } else if (field <= 4) {                      // field 0, or a known field's wrong type
-            return HQ_E_INVAL;
-        } else if (!r.skip(wt)) {
-            return HQ_E_INVAL;
-        }
-    }
+    const int rc = hqw::walk_batch(
+        bytes, len, bi,
+        [&](size_t field, size_t body, size_t n) {
+            if (bi.n_messages >= UINT32_MAX) return HQ_E_INVAL;   // (a span's `first` is 32 bits)
+            s.add(base + field, body + n - field, (uint32_t)bi.n_messages);
+            return HQ_OK;
+        },
+        [&] { s.close(); });                          // a span is `requests` fields back to back
+    if (rc) return rc;
     s.close();
-    bi.n_messages = count;
     *n_spans = s.n;
     if (info) *info = bi;
     return spans && s.n > cap ? HQ_E_STATE : HQ_OK;

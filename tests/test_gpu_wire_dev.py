@@ -1,23 +1,24 @@
 """The wire decode on the device (dragonboat_amd/csrc/hq_wire_dev.hip) against the host decoder
 (hq_wire_decode_batch): hq_wire_frame_batch's spans decoded by hq_wire_decode_dev must give the
 host decoder's records field for field, and reject exactly the messages it rejects. Every
-comparison is exact."""
+comparison is exact. Both decoders are hq_wire_codec.h compiled twice, so the messages are
+wire_cases.py's, on which test_wire_codec.py holds the host decoder to the referee
+(wire_decode_ref.py); the rejections are held to the referee here as well."""
 import ctypes
-import json
-import os
 
 import numpy as np
 import pytest
 
 import step_random as sr
 import step_scenarios as sc
+import wire_cases
+import wire_decode_ref as ref
 import wire_encode as we
 from step_harness import OracleBackend, WireBackend, check_phase_order, event_record, same_step
+from wire_cases import FIX, random_fields
 
 pytestmark = pytest.mark.gpu
 
-FIX = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "wire_fixtures.json")))
-EDGES = [0, 127, 128, (1 << 32) - 1, 1 << 63, (1 << 64) - 1]     # 1- to 10-byte varints
 SIZES = (1, 63, 64, 65, 200)
 
 
@@ -31,43 +32,9 @@ def host_decode_one(hq, body):
     return rc != hq.HQ_OK, out[0]
 
 
-def random_fields(rng):
-    v = lambda: EDGES[int(rng.integers(len(EDGES)))] if rng.random() < 0.5 else \
-        int(rng.integers(0, 1 << int(rng.integers(1, 64))))
-    return dict(type=int(rng.integers(0, 26)), to=v(), frm=v(), cluster_id=v(), term=v(),
-                log_term=v(), log_index=v(), commit=v(), reject=bool(rng.random() < 0.5), hint=v(),
-                hint_high=v())
-
-
-def shuffled(rng, f):
-    """The same message in another valid encoding: fields in a random order, unknown fields of
-    every skippable wire type, an entry, a repeated scalar (the last one counts), the snapshot
-    present or not."""
-    parts = [we.f_varint(1, f["type"]), we.f_varint(2, f["to"]), we.f_varint(3, f["frm"]),
-             we.f_varint(4, f["cluster_id"]), we.f_varint(5, f["term"]),
-             we.f_varint(6, f["log_term"]), we.f_varint(7, f["log_index"]),
-             we.f_varint(8, f["commit"]), we.f_varint(9, 1 if f["reject"] else 0),
-             we.f_varint(10, f["hint"]), we.f_varint(13, f["hint_high"]),
-             we.f_bytes(11, we.entry(3, 4, b"cmd")),
-             we.f_varint(15, int(rng.integers(0, 1 << 62))), we.key(16, 1) + bytes(range(8)),
-             we.key(17, 5) + b"\xaa\xbb\xcc\xdd", we.f_bytes(18, b"\x80" * int(rng.integers(0, 9))),
-             we.f_varint((1 << 28) + 3, 7)]
-    if rng.random() < 0.5:
-        parts.append(we.f_bytes(12, we.snapshot()))
-    order = rng.permutation(len(parts))
-    body = b"".join(parts[i] for i in order)
-    return we.f_varint(5, f["term"] ^ 1) + body        # term repeated: the later value stays
-
-
 @pytest.fixture(scope="module")
 def parity_messages():
-    rng = np.random.default_rng(41)
-    out = []
-    for _ in range(2000):
-        f = random_fields(rng)
-        out.append(we.message(**f))
-        out.append(shuffled(rng, f))
-    return out
+    return wire_cases.parity_messages()
 
 
 def lay_out(hq, batches, aligns):
@@ -153,28 +120,11 @@ def test_rejection_parity(hq, gpu_ctx):
     in a `requests` framing of its own (so the batch is well framed by construction), in one
     launch: status[i] is whether the host decoder rejects slice i; equal records where it does
     not."""
-    slices, owner = [], []
-    fixtures = []
-    for fx in FIX["batches"]:
-        raw = bytes.fromhex(fx["hex"])
-        assert raw[0] == 0x0A and raw[1] < 0x80
-        fixtures += [raw[2:2 + raw[1]], raw]   # the message, and the fixture's bytes taken as one
-    for k, m in enumerate(fixtures):
-        for n in range(len(m)):
-            slices.append(m[:n])
-            owner.append(k)
-        for i, b in enumerate(m):
-            for v in (0x00, 0x7F, 0x80, 0xFF, b ^ 1, b ^ 0x80):
-                slices.append(m[:i] + bytes([v]) + m[i + 1:])
-                owner.append(k)
-    for fx in FIX["malformed"]:
-        raw = bytes.fromhex(fx["hex"])
-        slices.append(raw[2:2 + raw[1]] if raw[0] == 0x0A else raw)
-        owner.append(-1)
-    assert len(slices) > 1100
-    ref = [host_decode_one(hq, s) for s in slices]
-    rejected = np.array([r for r, _ in ref])
-    for k in range(0, len(fixtures), 2):    # both outcomes for every fixture's message
+    slices, owner, n_fixtures = wire_cases.rejection_slices()
+    host = [host_decode_one(hq, s) for s in slices]
+    rejected = np.array([r for r, _ in host])
+    assert list(rejected) == [ref.rejected(s) for s in slices]
+    for k in range(0, n_fixtures, 2):    # both outcomes for every fixture's message
         mine = rejected[np.array(owner) == k]
         assert mine.any() and not mine.all(), k
     data = b"".join(we.f_bytes(1, s) for s in slices)
@@ -183,7 +133,7 @@ def test_rejection_parity(hq, gpu_ctx):
     got, status = hq.decode_dev(gpu_ctx, data, spans, len(slices))
     np.testing.assert_array_equal(status, rejected.astype(np.uint8))
     ok = ~rejected
-    want = np.array([m for _, m in ref], hq.WIRE_MESSAGE_DTYPE)
+    want = np.array([m for _, m in host], hq.WIRE_MESSAGE_DTYPE)
     assert got[ok].tobytes() == want[ok].tobytes()
 
 

@@ -19,7 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIX = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "wire_fixtures.json")))
 
 
-# ---- the reference walk of the framing (hq_wire.cpp parse_batch, without the message decode) ----
+# ---- the reference walk of the framing (hq_wire_codec.h walk_batch, without the message decode) ----
 class Malformed(Exception):
     pass
 

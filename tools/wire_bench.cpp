@@ -7,7 +7,7 @@
 // handle = its position), so no GPU is needed: it is for A/B of decoder builds on the box's CPU
 // (profiles/r06w/). Build it as the library builds its host sources (g++ -O3):
 //   g++ -O3 -std=c++17 -fPIC -o wire_bench tools/wire_bench.cpp dragonboat_amd/csrc/hq_wire.cpp \
-//       dragonboat_amd/csrc/hq_stream.cpp -pthread
+//       dragonboat_amd/csrc/hq_wire_frame.cpp dragonboat_amd/csrc/hq_stream.cpp -pthread
 //   wire_bench [G] [reps]      (WB_REVERSE=1: one batch in reverse group order)
 // The line ends with a digest of the stream: two decoders must print the same one.
 #include <algorithm>
@@ -18,6 +18,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "../dragonboat_amd/csrc/hq_wire_dev.h"
 #include "../include/hipquorum.h"
 
 // the stub worker: G groups, cluster id base + i * stride at handle i
@@ -34,6 +35,20 @@ extern "C" int hq_worker_find(hq_worker *w, uint64_t cid, uint32_t *handle) {
 extern "C" int hq_worker_group_count(hq_worker *w, uint64_t *n) {
     *n = w->n;
     return HQ_OK;
+}
+
+// the wire's device mode (hq_wire_dev.hip): never entered here (hq_wire_attach, not _device)
+int hq_wire_dev_open(hq_worker *, hq_wire_dev **) { return HQ_E_DEVICE; }
+void hq_wire_dev_close(hq_wire_dev *) {}
+const char *hq_wire_dev_error(const hq_wire_dev *) { return ""; }
+void hq_wire_dev_reset(hq_wire_dev *) {}
+int hq_wire_dev_add_batch(hq_wire_dev *, const uint8_t *, size_t, const hq_wire_span *, uint64_t,
+                          uint64_t, uint32_t) {
+    return HQ_E_DEVICE;
+}
+int hq_wire_dev_step(hq_wire_dev *, const hqs::WireEvent *, uint64_t, hq_step_output *, uint64_t[4],
+                     const uint32_t **, uint64_t *, uint64_t *) {
+    return HQ_E_DEVICE;
 }
 
 static double now_s() {
