@@ -5,14 +5,18 @@ HIPFLAGS ?= -O3 -std=c++17 -fPIC -Wall -Wno-unused-result --offload-arch=$(ARCH)
 CSRC := dragonboat_amd/csrc
 LIBDIR := dragonboat_amd/lib
 LIB := $(LIBDIR)/libhipquorum.so
-OBJS := $(LIBDIR)/hq_runtime.o $(LIBDIR)/hq_kernels.o $(LIBDIR)/hq_table.o $(LIBDIR)/hq_pack.o \
-        $(LIBDIR)/hq_worker.o $(LIBDIR)/hq_wire.o $(LIBDIR)/hq_stream.o $(LIBDIR)/hq_jobs.o $(LIBDIR)/hq_dstep.o \
-        $(LIBDIR)/hq_engine.o $(LIBDIR)/hq_wire_frame.o $(LIBDIR)/hq_wire_dev.o $(LIBDIR)/hq_heartbeat.o \
-        $(LIBDIR)/hq_heartbeat_wire.o
-SRCS := $(CSRC)/hq_kernels.hip $(CSRC)/hq_table.hip $(CSRC)/hq_runtime.hip $(CSRC)/hq_pack.cpp \
-        $(CSRC)/hq_worker.cpp $(CSRC)/hq_wire.cpp $(CSRC)/hq_stream.cpp $(CSRC)/hq_jobs.cpp $(CSRC)/hq_dstep.hip \
-        $(CSRC)/hq_engine.hip $(CSRC)/hq_wire_frame.cpp $(CSRC)/hq_wire_dev.hip $(CSRC)/hq_heartbeat.hip \
-        $(CSRC)/hq_heartbeat_wire.hip
+OBJS := $(LIBDIR)/hq_runtime.o $(LIBDIR)/hq_commit.o $(LIBDIR)/hq_commit_tiles.o \
+        $(LIBDIR)/hq_commit_lag.o $(LIBDIR)/hq_bits.o $(LIBDIR)/hq_ri_multi.o $(LIBDIR)/hq_synth.o \
+        $(LIBDIR)/hq_ingest.o $(LIBDIR)/hq_table.o $(LIBDIR)/hq_pack.o $(LIBDIR)/hq_worker.o \
+        $(LIBDIR)/hq_wire.o $(LIBDIR)/hq_stream.o $(LIBDIR)/hq_jobs.o $(LIBDIR)/hq_dstep.o \
+        $(LIBDIR)/hq_engine.o $(LIBDIR)/hq_wire_frame.o $(LIBDIR)/hq_wire_dev.o \
+        $(LIBDIR)/hq_heartbeat.o $(LIBDIR)/hq_heartbeat_wire.o
+SRCS := $(CSRC)/hq_runtime.hip $(CSRC)/hq_commit.hip $(CSRC)/hq_commit_tiles.hip \
+        $(CSRC)/hq_commit_lag.hip $(CSRC)/hq_bits.hip $(CSRC)/hq_ri_multi.hip $(CSRC)/hq_synth.hip \
+        $(CSRC)/hq_ingest.hip $(CSRC)/hq_table.hip $(CSRC)/hq_pack.cpp $(CSRC)/hq_worker.cpp \
+        $(CSRC)/hq_wire.cpp $(CSRC)/hq_stream.cpp $(CSRC)/hq_jobs.cpp $(CSRC)/hq_dstep.hip \
+        $(CSRC)/hq_engine.hip $(CSRC)/hq_wire_frame.cpp $(CSRC)/hq_wire_dev.hip \
+        $(CSRC)/hq_heartbeat.hip $(CSRC)/hq_heartbeat_wire.hip
 DEPS := $(wildcard $(CSRC)/*.h) include/hipquorum.h
 CXX ?= g++
 CXXFLAGS ?= -O3 -std=c++17 -fPIC -pthread -Wall -Wextra
@@ -39,16 +43,8 @@ oracle:
 	$(MAKE) -C oracle
 
 # tuning variants (one library each, for A/B runs via HQ_LIB_PATH, tools/ab_libs.sh):
-#   lib_vec2   lag kernels with 2 groups per lane (8-byte loads)
-#   lib_b512   every commit kernel with 512-thread blocks
-#   lib_mbN    grid cap (in 256-thread units) raised N x
 #   lib_ivN    records per lane of the table ingest kernels
-#   lib_b3tpwN tiles per wave of the 3-byte bitmap kernel
-#   lib_pltpwN tiles per wave of the bit-plane kernel, lib_plblkN its block size
 #   lib_swN    the device step engine's kernels asked for N waves per SIMD
-#   lib_rinet0 multi-ctx ReadIndex with the 28-CE transposition sort instead of Batcher's 19-CE network
-#   lib_tilecopy / lib_b3copy / lib_plcopy the commit tile / 3-byte / bit-plane kernel's loads and stores without the
-#              decision (their floors)
 #   lib_ingnostore / lib_ingnoload the grouped table ingest without its table stores / loads (timing probes: wrong output)
 #   lib_encspawn the threaded event encoder spawning its threads per call (before the task pool)
 #   lib_encprof the threaded encoder's per-range start / barrier arrival per call (stderr)
@@ -58,43 +54,19 @@ define variant
 	@mkdir -p $(dir $@)
 	$(HIPCC) $(HIPFLAGS) $(1) -shared -o $@ $(SRCS)
 endef
-tools/lib_vec2/libhipquorum.so: $(SRCS) $(DEPS)
-	$(call variant,-DHQ_LAG_VEC=2)
-tools/lib_b512/libhipquorum.so: $(SRCS) $(DEPS)
-	$(call variant,-DHQ_COMMIT_BLOCK_BIG=512)
-tools/lib_mb%/libhipquorum.so: $(SRCS) $(DEPS)
-	$(call variant,-DHQ_MAX_BLOCKS=$*)
 tools/lib_iv%/libhipquorum.so: $(SRCS) $(DEPS)
 	$(call variant,-DHQ_INGEST_V=$*)
-tools/lib_b3tpw%/libhipquorum.so: $(SRCS) $(DEPS)
-	$(call variant,-DHQ_BITS3_TPW=$*)
-tools/lib_pltpw%/libhipquorum.so: $(SRCS) $(DEPS)
-	$(call variant,-DHQ_PLANES_TPW=$*)
-tools/lib_plblk%/libhipquorum.so: $(SRCS) $(DEPS)
-	$(call variant,-DHQ_PLANES_BLK=$*)
-tools/lib_plplain/libhipquorum.so: $(SRCS) $(DEPS)
-	$(call variant,-DHQ_PLANES_PLAIN)
-tools/lib_plcopy/libhipquorum.so: $(SRCS) $(DEPS)
-	$(call variant,-DHQ_PLANES_COPY)
-tools/lib_tilecopy/libhipquorum.so: $(SRCS) $(DEPS)
-	$(call variant,-DHQ_TILE_COPY)
-tools/lib_b3copy/libhipquorum.so: $(SRCS) $(DEPS)
-	$(call variant,-DHQ_BITS3_COPY)
-
-variants: tools/lib_vec2/libhipquorum.so tools/lib_b512/libhipquorum.so
 
 clean:
 	rm -rf $(LIBDIR) oracle/build
 
-.PHONY: all oracle clean variants
+.PHONY: all oracle clean
 tools/lib_encspawn/libhipquorum.so: $(SRCS) $(DEPS)
 	$(call variant,-DHQ_ENCODE_SPAWN)
 tools/lib_ingnostore/libhipquorum.so: $(SRCS) $(DEPS)
 	$(call variant,-DHQ_INGEST_NOSTORE)
 tools/lib_ingnoload/libhipquorum.so: $(SRCS) $(DEPS)
 	$(call variant,-DHQ_INGEST_NOLOAD)
-tools/lib_rinet0/libhipquorum.so: $(SRCS) $(DEPS)
-	$(call variant,-DHQ_RI_NET=0)
 tools/lib_encprof/libhipquorum.so: $(SRCS) $(DEPS)
 	$(call variant,-DHQ_ENC_PROF)
 tools/lib_engprof/libhipquorum.so: $(SRCS) $(DEPS)
@@ -112,12 +84,8 @@ tools/lib_bintpb%/libhipquorum.so: $(SRCS) $(DEPS)
 tools/binprof: tools/binprof.hip $(SRCS) $(DEPS) $(OBJS)
 	$(HIPCC) $(HIPFLAGS) -c -o tools/binprof.o tools/binprof.hip
 	$(HIPCC) $(HIPFLAGS) -pthread -o $@ tools/binprof.o $(filter-out $(LIBDIR)/hq_table.o,$(OBJS))
-tools/lib_plcqtpw%/libhipquorum.so: $(SRCS) $(DEPS)
-	$(call variant,-DHQ_PLCQ_TPW=$*)
 tools/lib_stepchunks%/libhipquorum.so: $(SRCS) $(DEPS)
 	$(call variant,-DHQ_STEP_CHUNKS=$*)
-tools/lib_plcqzero%/libhipquorum.so: $(SRCS) $(DEPS)
-	$(call variant,-DHQ_PLCQ_ZERO_EARLY=$*)
 # persistent-engine experiments (tools/ab_engine.py): multi-batch loop / flat / claim kernels beside
 # the engine, in a library of their own linked against the product library
 tools/lib_engexp/libengexp.so: tools/engine_exp.hip $(LIB) $(DEPS)

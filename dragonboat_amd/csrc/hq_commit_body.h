@@ -1,16 +1,14 @@
-// hq_commit_body.h — the commit decision shared by the launch-per-step kernels (hq_kernels.hip)
-// and the persistent commit engine (hq_engine.hip): the u64 selection networks, the term-check
-// forms and the body that decides one 128-group tile (HQ_LAYOUT_TILES / _TILES_LEADER).
+// hq_commit_body.h — the commit decision shared by the launch-per-step kernels (hq_commit.h)
+// and the persistent commit engine (hq_engine.hip): the kernel argument structs, the u64 selection
+// networks, the term-check forms and the body that decides one 128-group tile (HQ_LAYOUT_TILES /
+// _TILES_LEADER).
 #pragma once
 
 #include <type_traits>
 
-#include "hq_internal.h"
+#include "hq_launch.h"
 
 namespace {
-
-typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 // Streaming columns are read once: nontemporal loads (measured ~6 % faster than plain ones on
 // the 1M x 3 commit stream, tools/kexp.hip, git history). The committed column is stored with plain stores:
@@ -40,6 +38,26 @@ struct CommitK {
     uint32_t R, reserved;
 };
 static_assert(sizeof(CommitK) == 96, "keep the decision kernels' argument at 96 bytes");
+
+// Every field of a column batch (the generator, hq_synth.hip, and the tile packer,
+// hq_commit_tiles.hip, write / read them all).
+struct CommitCols {
+    uint64_t G, stride, nwords;
+    uint32_t n_max, R;
+    const uint64_t *match;
+    const uint8_t *nv;
+    const uint64_t *cin;
+    uint64_t *cout;
+    const uint64_t *last;
+    const uint64_t *tstart;
+    const uint64_t *term;
+    const uint64_t *ring;
+    uint64_t *changed;
+    uint64_t *fallback;
+    const uint16_t *mask;
+    const uint32_t *ring32;
+    uint64_t tile_words;   // HQ_LAYOUT_TILES: u64 words per tile
+};
 
 // ---- compare-exchange networks over u64 held in registers --------------------------------
 __device__ __forceinline__ void ce(uint64_t &a, uint64_t &b) {
@@ -87,16 +105,6 @@ __device__ __forceinline__ uint64_t quorum_match_pern(uint64_t (&v)[N], int n) {
 #pragma unroll
     for (int k = 0; k < N; ++k) r = (k == idx) ? v[k] : r;
     return r;
-}
-
-__device__ __forceinline__ uint64_t spread32(uint32_t x) {  // bit i -> bit 2i
-    uint64_t v = x;
-    v = (v | (v << 16)) & 0x0000FFFF0000FFFFull;
-    v = (v | (v << 8)) & 0x00FF00FF00FF00FFull;
-    v = (v | (v << 4)) & 0x0F0F0F0F0F0F0F0Full;
-    v = (v | (v << 2)) & 0x3333333333333333ull;
-    v = (v | (v << 1)) & 0x5555555555555555ull;
-    return v;
 }
 
 // One group's decision given its packed matches. FORM 0 = term-start, 1 = ring gather,
@@ -149,12 +157,6 @@ __device__ __forceinline__ void decide(const CommitK &a, uint64_t g, uint64_t (&
     }
     cout = chg ? q : cin;
 }
-
-// 1: the tile bodies issue every row load before the first compare (tile_blocks); 0 is the
-// A/B baseline of profiles/r01i/kexp10_sched_barrier_ab.log
-#ifndef HQ_TILE_SCHED_BARRIER
-#define HQ_TILE_SCHED_BARRIER 1
-#endif
 
 // One 128-group tile starting at group `wbase` (a multiple of HQ_TILE_GROUPS), decided by one
 // wave (`lane` = this lane). Row position 2i holds group i of the tile and position 2i + 1 group
@@ -218,31 +220,16 @@ __device__ __forceinline__ void commit_tile(const CommitK &a, uint64_t wbase, ui
         } else {
             ax = ld_stream2(row(NR + 2));
         }
-#if HQ_TILE_SCHED_BARRIER
         // every row load of the tile is issued before the first compare: otherwise the
         // scheduler starts the network after two rows and issues the rows past the 4-KiB
         // immediate-offset range behind an s_waitcnt, one memory latency later (n <= 5: the
-        // wider bodies would spill inside the 64-VGPR fused kernel)
+        // wider bodies would spill inside the 64-VGPR fused kernel;
+        // profiles/r01i/kexp10_sched_barrier_ab.log)
         if constexpr (N <= 5) __builtin_amdgcn_sched_barrier(0);
-#endif
         const int na = PERN ? (int)a.nv[ga] : N, nb = PERN ? (int)a.nv[gb] : N;
         uint64_t coa, cob;
-#ifdef HQ_TILE_COPY   // tuning floor: the same loads and stores, no decision (wrong results)
-        coa = ci.x ^ la.x ^ ax.x;
-        cob = ci.y ^ la.y ^ ax.y;
-#pragma unroll
-        for (int s = LEAD; s < N; ++s) {
-            coa ^= m0[s];
-            cob ^= m1[s];
-        }
-        ca = coa & 1;
-        cb = cob & 1;
-        (void)na;
-        (void)nb;
-#else
         decide<N, FORM, PERN>(a, ga, m0, na, ci.x, la.x, ax.x, coa, ca, fa);
         decide<N, FORM, PERN>(a, gb, m1, nb, ci.y, la.y, ax.y, cob, cb, fb);
-#endif
         if constexpr (INPLACE) {
             // the lane's 16 bytes of the committed row it has just read (groups ga, gb)
             uint64_t *cr = const_cast<uint64_t *>(row(NR));

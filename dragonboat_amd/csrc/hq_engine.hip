@@ -44,6 +44,7 @@
 #include <thread>
 
 #include "hq_commit_body.h"
+#include "hq_launch.h"
 
 namespace {
 
@@ -581,36 +582,20 @@ void engine_kernel_for(bool sig, EngineKernel *fn, int *blk) {
     *blk = B;
 }
 
-template <int N>
-int engine_kernel_n(uint32_t form, uint32_t layout, bool sig, EngineKernel *fn, int *blk) {
-    const bool lead = (layout & 0xFFu) == HQ_LAYOUT_TILES_LEADER;
-    const bool inplace = (layout & HQ_LAYOUT_IN_PLACE) != 0;
-#define HQ_ENGINE_PICK(F)                                                                        \
-    if (inplace) engine_kernel_for<N, F, 1, true>(sig, fn, blk);                                 \
-    else if (lead) engine_kernel_for<N, F, 1, false>(sig, fn, blk);                              \
-    else engine_kernel_for<N, F, 0, false>(sig, fn, blk);
-    if (form == HQ_FORM_TERM_MASK) {
-        HQ_ENGINE_PICK(HQ_FORM_TERM_MASK)
-    } else {
-        HQ_ENGINE_PICK(HQ_FORM_TERM_START)
-    }
-#undef HQ_ENGINE_PICK
-    return HQ_OK;
-}
-
 // sig: per-step completion signals (write-through stores: a step's outputs are visible once its
 // waves' stores have drained)
 int engine_kernel(uint32_t n, uint32_t form, uint32_t layout, bool sig, EngineKernel *fn, int *blk) {
-    switch (n) {
-    case 1: return engine_kernel_n<1>(form, layout, sig, fn, blk);
-    case 2: return engine_kernel_n<2>(form, layout, sig, fn, blk);
-    case 3: return engine_kernel_n<3>(form, layout, sig, fn, blk);
-    case 4: return engine_kernel_n<4>(form, layout, sig, fn, blk);
-    case 5: return engine_kernel_n<5>(form, layout, sig, fn, blk);
-    case 6: return engine_kernel_n<6>(form, layout, sig, fn, blk);
-    case 7: return engine_kernel_n<7>(form, layout, sig, fn, blk);
-    default: return engine_kernel_n<8>(form, layout, sig, fn, blk);
-    }
+    // 2: the leader tiles in place, 1: leader tiles, 0: tiles with the leader's row
+    const int tiles = (layout & HQ_LAYOUT_IN_PLACE) ? 2 : (layout & 0xFFu) == HQ_LAYOUT_TILES_LEADER;
+    dispatch_n(n, [&](auto nn) {
+        dispatch<HQ_FORM_TERM_MASK, HQ_FORM_TERM_START>(form, [&](auto f) {
+            dispatch<2, 1, 0>(tiles, [&](auto t) {
+                constexpr int T = decltype(t)::value;
+                engine_kernel_for<decltype(nn)::value, decltype(f)::value, (T > 0), T == 2>(sig, fn, blk);
+            });
+        });
+    });
+    return HQ_OK;
 }
 
 }  // namespace

@@ -1,4 +1,4 @@
-// hq_internal.h — shared between the runtime (hq_runtime.hip) and the kernels (hq_kernels.hip).
+// hq_internal.h — shared between the runtime (hq_runtime.hip) and the kernel files (hq_*.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -24,8 +24,6 @@ struct hq_ctx {
     uint64_t begin_after = 0;
     double timed_ms = 0.0;
     uint64_t timed_launches = 0;
-    // launch geometry of the bitmap kernels (256; HQ_BITS_BLOCK=512|1024 at hq_open)
-    int bits_block = 256;
     // multi-ctx ReadIndex two groups per lane when the batch allows it (HQ_RI_PAIRS=0: off, A/B)
     bool ri_pairs = true;
     // uniform multi-ctx tiles (K_max in {2, 4, 8}, n = n_max) on k_ri_tiles_u (HQ_RI_UNIFORM=0:

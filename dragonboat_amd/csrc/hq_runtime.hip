@@ -1,5 +1,6 @@
 // hq_runtime.hip — contexts, memory, timing and the host-pointer entry points of
-// libhipquorum.so. Kernels and their _dev launchers live in hq_kernels.hip.
+// libhipquorum.so. Kernels and their _dev launchers live in the family files (hq_commit.hip, hq_commit_tiles.hip,
+// hq_commit_lag.hip, hq_bits.hip, hq_ri_multi.hip, hq_synth.hip, hq_ingest.hip).
 #include <cstdlib>
 #include <cstring>
 #include <new>
@@ -125,10 +126,6 @@ int hq_open(int device, uint32_t flags, hq_ctx **out) {
     hq_ctx *ctx = new (std::nothrow) hq_ctx();
     if (!ctx) return hq::fail(nullptr, HQ_E_NOMEM, "hq_open: out of host memory");
     ctx->device = device;
-    if (const char *b = std::getenv("HQ_BITS_BLOCK")) {
-        const int v = std::atoi(b);
-        if (v == 256 || v == 512 || v == 1024) ctx->bits_block = v;
-    }
     if (const char *r = std::getenv("HQ_RI_PAIRS")) ctx->ri_pairs = std::atoi(r) != 0;
     if (const char *r = std::getenv("HQ_RI_UNIFORM")) ctx->ri_uniform = std::atoi(r) != 0;
     if (const char *gd = std::getenv("HQ_BIN_GRID")) {

@@ -1,6 +1,6 @@
 """Golden output digests of the BASELINE configs at full size (SURVEY.md §8c "golden vectors for
 large configs"): the inputs are the deterministic generator's (oracle/qgen.c, its device twin in
-hq_kernels.hip) at the seeds below, the outputs the oracle's (oracle/qref.c) decisions, and only
+hq_synth.hip) at the seeds below, the outputs the oracle's (oracle/qref.c) decisions, and only
 their SHA-256 digests (plus counts) are committed, in config_digests.json. The CPU tests check the
 oracle still reproduces them; the GPU tests check the kernels produce the same bytes from the
 device generator's inputs, in the headline layouts.

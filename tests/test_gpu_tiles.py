@@ -199,7 +199,7 @@ def test_tiled_validation(gpu_ctx, hq):
 
 @pytest.mark.parametrize("tiled", [False, True])
 def test_commit_grid_stride_beyond_cap(gpu_ctx, hq, tiled):
-    """More groups than one capped grid covers (HQ_MAX_BLOCKS x 256 threads, two groups per
+    """More groups than one capped grid covers (kMaxBlocks x 256 threads, two groups per
     lane = 8M groups): the grid-stride loop's second iteration, columns and tiles, bit-exact."""
     G, n = (8 << 20) + 4099, 5
     form = hq.HQ_FORM_TERM_MASK

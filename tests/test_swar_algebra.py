@@ -1,4 +1,4 @@
-"""CPU check of the SWAR identities the bitmap kernel (k_bits in hq_kernels.hip) relies on: four
+"""CPU check of the SWAR identities the bitmap kernel (k_bits in hq_bits.hip) relies on: four
 groups per 32-bit word, byte-wise popcount / compare, v_perm_b32 byte lookup for (1 << n) - 1.
 The formulas are restated here in Python and compared against the per-group scalar rule on
 random words, including invalid n and ragged tails. (The kernel itself is checked against the
