@@ -416,6 +416,12 @@ int hq_wire_add_locals(hq_wire *w, uint64_t n, const uint64_t *cluster_ids, cons
 // spans queued for hq_wire_step_device
 static int add_batch_device(hq_wire *w, const uint8_t *bytes, size_t len) {
     const uint32_t index = w->batch_calls++;
+    if (hq_wire_dev_framing(w->dev)) {               // framed at the step, on the device
+        const int rc = hq_wire_dev_queue(w->dev, bytes, len, index);
+        if (rc) return w->fail(rc, hq_wire_dev_error(w->dev));
+        w->dev_queued++;
+        return HQ_OK;
+    }
     if (w->spans.empty()) w->spans.resize(1024);
     hq_wire_batch_info bi;
     uint64_t ns = 0;
@@ -667,22 +673,44 @@ int hq_wire_step_sized(hq_wire *w, uint8_t *bytes, uint64_t cap, uint16_t *sizes
 int hq_wire_step_device(hq_wire *w, hq_step_output *out, hq_wire_stats *stats) {
     if (!w || !out) return HQ_E_INVAL;
     if (!w->dev) return w->fail(HQ_E_STATE, "hq_wire_step_device: no device worker attached");
-    uint64_t c[4], rejected_bytes = 0;
+    uint64_t c[4], rejected_bytes = 0, n_bad_message = 0;
+    hq_wire_stats add{};
     const int rc = hq_wire_dev_step(w->dev, static_cast<const hqs::WireEvent *>(w->recs.data()),
                                     w->recs.size(), out, c, &w->rejected, &w->n_rejected,
-                                    &rejected_bytes);
+                                    &rejected_bytes, &n_bad_message, &add);
     if (rc) return w->fail(rc, hq_wire_dev_error(w->dev));
     if (stats) {
-        // the kernels' counters beside the host's; a batch dropped for a malformed message is
-        // counted nowhere (as one hq_wire_add_batch rejects)
+        // the kernels' counters beside the host's (with the framing on the device, the batches'
+        // own counts come from its results); a batch dropped for a malformed message is counted
+        // nowhere (as one hq_wire_add_batch rejects)
         *stats = w->stats;
+        stats->batches += add.batches;
+        stats->bytes += add.bytes;
+        stats->dropped_batches += add.dropped_batches;
+        stats->dropped_messages += add.dropped_messages;
         stats->messages += c[0];
         stats->entries += c[1];
         stats->snapshot_received += c[2];
         stats->dropped_no_cluster += c[3];
-        stats->batches -= w->n_rejected;
+        stats->batches -= n_bad_message;
         stats->bytes -= rejected_bytes;
     }
+    return HQ_OK;
+}
+
+int hq_wire_set_device_framing(hq_wire *w, int on) {
+    if (!w) return HQ_E_INVAL;
+    if (!w->dev) return w->fail(HQ_E_STATE, "hq_wire_set_device_framing: no device worker attached");
+    if (!w->recs.empty() || w->dev_queued)
+        return w->fail(HQ_E_STATE, "hq_wire_set_device_framing: events queued (reset first)");
+    hq_wire_dev_set_framing(w->dev, on != 0, w->deployment_id);
+    return HQ_OK;
+}
+
+int hq_wire_device_frame_stats(hq_wire *w, uint64_t out[4]) {
+    if (!w || !out) return HQ_E_INVAL;
+    if (!w->dev) return w->fail(HQ_E_STATE, "hq_wire_device_frame_stats: no device worker attached");
+    hq_wire_dev_frame_stats(w->dev, out);
     return HQ_OK;
 }
 

@@ -1,9 +1,9 @@
 // hq_wire_codec.h — the one protobuf reader and writer of raftpb.Message (raft.proto:154-168) and
 // raftpb.MessageBatch (:191-196), and the cluster-id table beside them. One source for the host
-// decoder and encoder (hq_wire.cpp), the framer (hq_wire_frame.cpp), the decode kernels
-// (hq_wire_dev.hip), the heartbeat marshaller (hq_heartbeat_wire.h: host worker and kernels) and
-// the stand-alone sanitizer programs of the tests, so what runs on the GPU runs on the CPU under
-// sanitizers first. Plain C++17 over <cstdint> and the public header. No table, no array indexed
+// decoder and encoder (hq_wire.cpp), the framer (hq_wire_frame.cpp) and the framing kernels
+// (hq_wire_frame_dev.hip: the segment walker below), the decode kernels (hq_wire_dev.hip), the
+// heartbeat marshaller (hq_heartbeat_wire.h: host worker and kernels) and the stand-alone
+// sanitizer programs of the tests, so what runs on the GPU runs on the CPU under sanitizers first. Plain C++17 over <cstdint> and the public header. No table, no array indexed
 // by a variable: the kernels keep everything in registers.
 //
 // What the reader accepts is any valid proto2 encoding (as Message.Unmarshal raft.pb.go:4831 /
@@ -32,9 +32,10 @@ constexpr uint32_t kSnapshotReceived = 22;   // raft.proto MessageType
 // pointer difference) on the host.
 
 // LEB128 at b[p ..): false at `end` before the last byte, or past 64 bits. The host takes the
-// common one-byte varint first; the kernels keep the loop rolled.
-template <class I>
-HQ_WIRE_HD bool varint(const uint8_t *b, I &p, I end, uint64_t &v) {
+// common one-byte varint first; the kernels keep the loop rolled. B is `const uint8_t *`, or
+// anything else that gives the byte at a position by b[p] (Window below).
+template <class I, class B>
+HQ_WIRE_HD bool varint(B b, I &p, I end, uint64_t &v) {
 #if !defined(__HIP_DEVICE_COMPILE__)
     if (p < end && b[p] < 0x80) {
         v = b[p++];
@@ -76,8 +77,8 @@ HQ_WIRE_HD uint32_t varint_error(I p0, I p) {
 }
 
 // a field of wire type wt hopped over (skipRaft, raft.pb.go:6293): kOk or why not
-template <class I>
-HQ_WIRE_HD uint32_t skip(const uint8_t *b, I &p, I end, uint32_t wt) {
+template <class I, class B>
+HQ_WIRE_HD uint32_t skip(B b, I &p, I end, uint32_t wt) {
     uint64_t n = 0;
     const I p0 = p;
     switch (wt) {
@@ -99,8 +100,8 @@ HQ_WIRE_HD uint32_t skip(const uint8_t *b, I &p, I end, uint32_t wt) {
 
 // the `requests` header at p: its body's position and length; false when it is not one, or runs
 // past end
-template <class I>
-HQ_WIRE_HD bool header(const uint8_t *b, I &p, I end, uint64_t &n) {
+template <class I, class B>
+HQ_WIRE_HD bool header(B b, I &p, I end, uint64_t &n) {
     uint64_t tag;
     if (!varint(b, p, end, tag)) return false;
     if ((uint32_t)(tag >> 3) != 1 || (uint32_t)(tag & 7) != 2) return false;
@@ -213,6 +214,234 @@ inline int walk_batch(const uint8_t *bytes, size_t len, hq_wire_batch_info &info
         info.n_messages++;
     }
     return HQ_OK;
+}
+
+// ---- framing by segments -------------------------------------------------------------------------
+// walk_batch's walk cut into pieces that can run side by side (hq_wire_frame_dev.hip; the host runs
+// the same code under sanitizers, tests/test_wire_frame_segments.py). A batch is cut at the fixed
+// positions k * S; segment k owns every field that STARTS in [k S, (k + 1) S), wherever it ends.
+// Walked from its entry (the first field start at or past k S) a segment gives its fields exactly
+// as walk_batch does, and its exit, the first field start at or past its end, which is the entry
+// of the next segment that is not swallowed by a long field. Segment 0 enters at 0; a later one
+// does not know its entry and guesses it (guess_entry). Nothing may depend on the guess:
+// chain_batch walks the segments' records in order and takes a segment only when its entry is the
+// exit handed to it, so by induction from segment 0 every segment it takes was walked from its
+// true entry; a wrong guess leaves the batch unconfirmed (framed again by walk_batch).
+
+// A stretch [lo, hi) of a batch kept at b (the kernels': in LDS); positions count from the batch
+struct Window {
+    const uint8_t *b;
+    uint64_t lo, hi;
+    HQ_WIRE_HD uint8_t operator[](uint64_t p) const { return b[p - lo]; }
+};
+// ... backed by the batch itself where the stretch ends (the guess's reads behind its window)
+struct WindowOver {
+    Window w;
+    const uint8_t *batch;
+    HQ_WIRE_HD uint8_t operator[](uint64_t p) const {
+        return p >= w.lo && p < w.hi ? w.b[p - w.lo] : batch[p];
+    }
+};
+
+constexpr uint32_t kFieldHead = 20;        // a field's tag and its length or value: two varints
+constexpr uint64_t kNoEntry = ~0ull;       // no guess
+constexpr uint32_t kGuessMessages = 4, kGuessFields = 8;
+enum : uint32_t { kSeenDeployment = 1, kSeenSource = 2, kSeenBinVer = 4 };
+
+struct Segment {                           // what the walk of one segment leaves
+    uint64_t entry, exit;
+    uint64_t n_messages, n_spans;          // spans: counted always, written while they fit
+    uint64_t deployment_id, source_address_len;
+    uint32_t bin_ver;
+    uint32_t seen;                         // kSeen*: the batch's own fields this segment set
+    uint32_t malformed;                    // walk_batch's HQ_E_INVAL, met from this entry
+    uint32_t pad;
+};
+
+struct SegmentWalk {                       // a segment's walk under way
+    Segment s;
+    uint64_t pos;                          // the next field's start
+    hq_wire_span cur;                      // the open span (count 0: none); `first` counts from
+};                                         // the segment's first message
+
+HQ_WIRE_HD void segment_begin(SegmentWalk &w, uint64_t entry) {
+    w = SegmentWalk{};
+    w.s.entry = w.s.exit = w.pos = entry;
+}
+
+template <class Put>
+HQ_WIRE_HD void span_close(SegmentWalk &w, Put &&put) {
+    if (!w.cur.count) return;
+    put(w.s.n_spans, w.cur);
+    w.s.n_spans++;
+    w.cur = hq_wire_span{};
+}
+
+// hq_wire_frame.cpp's rule: the field at [off, off + size) is the segment's next message
+template <class Put>
+HQ_WIRE_HD void span_add(SegmentWalk &w, uint64_t off, uint64_t size, Put &&put) {
+    const bool large = size > HQ_WIRE_SPAN_BYTES;
+    if (w.cur.count && (large || w.cur.count == HQ_WIRE_SPAN_MESSAGES ||
+                        w.cur.len + size > HQ_WIRE_SPAN_BYTES))
+        span_close(w, put);
+    if (!w.cur.count) {
+        w.cur.offset = off;
+        w.cur.first = (uint32_t)w.s.n_messages;
+    }
+    w.cur.len += size;
+    w.cur.count++;
+    if (large) {
+        w.cur.flags = HQ_WIRE_SPAN_LARGE;
+        span_close(w, put);
+    }
+    w.s.n_messages++;
+}
+
+// The walk from w.pos on, over bytes b that hold the batch's [.., hi) (hi <= len, the batch's
+// length): every field that starts before seg_end, as walk_batch takes it; put(i, span) for the
+// segment's i-th span. true: the segment is done (w.s.exit or w.s.malformed set; the open span
+// closed); false: the field at w.pos needs bytes behind hi (it is walked only with kFieldHead
+// bytes or the batch's end in sight: call again with a window that starts at w.pos).
+template <class B, class Put>
+HQ_WIRE_HD bool walk_segment(const B &b, uint64_t hi, uint64_t len, uint64_t seg_end,
+                             SegmentWalk &w, Put &&put) {
+    const uint64_t end = len;
+    while (w.pos < seg_end) {
+        uint64_t p = w.pos;
+        if (hi < len && p + kFieldHead > hi) return false;
+        const uint64_t f0 = p;
+        uint64_t n;
+        if (end - p >= 2 && b[p] == 0x0a && b[p + 1] < 0x80) {
+            n = b[p + 1];
+            p += 2;
+            if (end - p < n) return w.s.malformed = 1, true;
+        } else {
+            uint64_t tag;
+            if (!varint(b, p, end, tag)) return w.s.malformed = 1, true;
+            const uint32_t field = (uint32_t)(tag >> 3), wt = (uint32_t)(tag & 7);
+            if (field != 1 || wt != 2) {
+                span_close(w, put);
+                uint64_t v;
+                if (field == 2 && wt == 0) {
+                    if (!varint(b, p, end, v)) return w.s.malformed = 1, true;
+                    w.s.deployment_id = v;
+                    w.s.seen |= kSeenDeployment;
+                } else if (field == 3 && wt == 2) {
+                    if (!varint(b, p, end, v) || end - p < v) return w.s.malformed = 1, true;
+                    p += v;
+                    w.s.source_address_len = v;
+                    w.s.seen |= kSeenSource;
+                } else if (field == 4 && wt == 0) {
+                    if (!varint(b, p, end, v)) return w.s.malformed = 1, true;
+                    w.s.bin_ver = (uint32_t)v;
+                    w.s.seen |= kSeenBinVer;
+                } else if (field <= 4) {
+                    return w.s.malformed = 1, true;
+                } else if (skip(b, p, end, wt) != kOk) {
+                    return w.s.malformed = 1, true;
+                }
+                w.pos = p;
+                continue;
+            }
+            if (!varint(b, p, end, n) || end - p < n) return w.s.malformed = 1, true;
+        }
+        p += n;
+        span_add(w, f0, p - f0, put);
+        w.pos = p;
+    }
+    span_close(w, put);
+    w.s.exit = w.pos;
+    return true;
+}
+
+// Whether fields may start at q (< len): kGuessMessages `requests` fields back to back, or at
+// most kGuessFields `requests` fields and fields of the batch's own (2, 3, 4) that end with the
+// batch. An unknown field is not taken: what a message holds (fields 5 and up, and fields 1 to 4
+// as varints) must not look like a batch. Reads at most kFieldHead bytes at each of at most
+// kGuessFields places.
+template <class B>
+HQ_WIRE_HD bool guess_at(const B &b, uint64_t q, uint64_t len) {
+    uint64_t p = q;
+    uint32_t messages = 0;
+    bool other = false;
+    for (uint32_t f = 0; f < kGuessFields; ++f) {
+        if (p == len) return true;
+        uint64_t tag, v;
+        if (!varint(b, p, len, tag)) return false;
+        const uint32_t field = (uint32_t)(tag >> 3), wt = (uint32_t)(tag & 7);
+        if (field == 1 && wt == 2) {
+            if (!varint(b, p, len, v) || len - p < v) return false;
+            p += v;
+            if (!other && ++messages == kGuessMessages) return true;
+        } else if ((field == 2 || field == 4) && wt == 0) {
+            other = true;
+            if (!varint(b, p, len, v)) return false;
+        } else if (field == 3 && wt == 2) {
+            other = true;
+            if (!varint(b, p, len, v) || len - p < v) return false;
+            p += v;
+        } else {
+            return false;
+        }
+    }
+    return p == len;
+}
+
+// the first q in [lo, hi) that guess_at takes, or kNoEntry
+template <class B>
+HQ_WIRE_HD uint64_t guess_entry(const B &b, uint64_t lo, uint64_t hi, uint64_t len) {
+    for (uint64_t q = lo; q < hi; ++q)
+        if (guess_at(b, q, len)) return q;
+    return kNoEntry;
+}
+
+// where segment k of a batch of len bytes cut every S bytes ends (it starts at k S)
+HQ_WIRE_HD uint64_t segment_end(uint64_t k, uint64_t S, uint64_t len) {
+    return (k + 1) * S < len ? (k + 1) * S : len;
+}
+HQ_WIRE_HD uint64_t segment_count(uint64_t S, uint64_t len) { return (len + S - 1) / S; }
+
+enum : uint32_t { kFramed = 0, kMalformed = 1, kSpansDidNotFit = 2, kUnconfirmed = 3 };
+
+struct SegmentPlace {                      // where a taken segment's output goes in its batch's;
+    uint64_t first_message, first_span;    // first_span == kNoEntry: void (inside a long field)
+};
+
+// The chain over a batch's n segment records: status, the batch's counts and fields into r,
+// each segment's place into place[0 .. n), the void segments counted. span_cap: what a
+// segment's span region holds.
+HQ_WIRE_HD void chain_batch(const Segment *seg, uint64_t n, uint64_t S, uint64_t len,
+                            uint64_t span_cap, SegmentPlace *place, hq_wire_frame_result &r,
+                            uint32_t &voids) {
+    r = hq_wire_frame_result{};
+    voids = 0;
+    uint64_t cur = 0;
+    bool fit = true;
+    for (uint64_t k = 0; k < n; ++k) {
+        if (cur >= segment_end(k, S, len)) {
+            place[k] = SegmentPlace{0, kNoEntry};
+            ++voids;
+            continue;
+        }
+        const Segment s = seg[k];
+        if (s.entry != cur) {
+            r.status = kUnconfirmed;
+            return;
+        }
+        place[k] = SegmentPlace{r.n_messages, r.n_spans};
+        r.n_messages += s.n_messages;
+        r.n_spans += s.n_spans;
+        fit = fit && s.n_spans <= span_cap;
+        if (s.seen & kSeenDeployment) r.deployment_id = s.deployment_id;
+        if (s.seen & kSeenSource) r.source_address_len = s.source_address_len;
+        if (s.seen & kSeenBinVer) r.bin_ver = s.bin_ver;
+        if (s.malformed || r.n_messages > UINT32_MAX) {      // (a span's `first` is 32 bits)
+            r.status = kMalformed;
+            return;
+        }
+        cur = s.exit;
+    }
+    if (!fit) r.status = kSpansDidNotFit;
 }
 
 // ---- writing -----------------------------------------------------------------------------------

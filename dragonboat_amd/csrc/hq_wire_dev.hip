@@ -7,7 +7,9 @@
 // The device mode of hq_wire (hq_wire_attach_device) follows in the same file: the decoded records
 // keyed by the worker's handle through a device hash table, sorted with the step's local events by
 // (handle, category), turned into rows and per-handle offsets, and handed to the device step
-// (hq_worker_step_device_rows) without returning to the host.
+// (hq_worker_step_device_rows) without returning to the host. With the framing on the device
+// (hq_wire_set_device_framing) the step first frames the queued batches (hq_wire_frame_dev.hip),
+// and the decode takes the spans where the framing left them.
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
@@ -280,6 +282,17 @@ struct hq_wire_dev {
     uint64_t *h_read = nullptr;                       // pinned: the counters and the rows' count
     uint32_t *h_bad = nullptr;
     size_t h_bad_cap = 0;
+    // the framing on the device (hq_wire_set_device_framing): the batches queued as they came,
+    // where the device reads them (refs: absolute addresses) and where the host does
+    bool framing = false;
+    uint64_t deployment_id = 0;
+    std::vector<hq_wire_batch_ref> refs;
+    std::vector<const uint8_t *> host_bytes;
+    std::vector<uint8_t> frame_rejected;              // per batch: a framing error
+    DevBuf d_refs, d_frame;                           // d_frame: totals, results, void segments
+    uint8_t *h_frame = nullptr;                       // pinned: d_frame read back
+    size_t h_frame_cap = 0;
+    uint64_t frame_stats[4] = {0, 0, 0, 0};
 
     int fail(int code, const std::string &m) {
         err = m;
@@ -361,12 +374,14 @@ void hq_wire_dev_close(hq_wire_dev *d) {
     (void)hipSetDevice(d->ctx->device);
     (void)hipStreamSynchronize(d->ctx->stream);
     for (DevBuf *b : {&d->d_slots, &d->d_spans, &d->d_span_batch, &d->d_bad, &d->d_recs, &d->d_cids,
-                      &d->d_keys, &d->d_vals, &d->d_events, &d->d_offsets, &d->d_counters, &d->d_tmp})
+                      &d->d_keys, &d->d_vals, &d->d_events, &d->d_offsets, &d->d_counters, &d->d_tmp,
+                      &d->d_refs, &d->d_frame})
         if (b->p) (void)hipFree(b->p);
     for (StageBlock &s : d->stage)
         if (s.host) (void)hipHostFree(s.host);
     if (d->h_read) (void)hipHostFree(d->h_read);
     if (d->h_bad) (void)hipHostFree(d->h_bad);
+    if (d->h_frame) (void)hipHostFree(d->h_frame);
     delete d;
 }
 
@@ -379,18 +394,31 @@ void hq_wire_dev_reset(hq_wire_dev *d) {
     d->batch_len.clear();
     d->n_msgs = 0;
     d->rejected.clear();
+    d->refs.clear();
+    d->host_bytes.clear();
     for (StageBlock &s : d->stage) s.fill = 0;
 }
 
-int hq_wire_dev_add_batch(hq_wire_dev *d, const uint8_t *bytes, size_t len, const hq_wire_span *spans,
-                          uint64_t n_spans, uint64_t n_messages, uint32_t index) {
-    if (d->n_msgs + n_messages >= (1ull << 31))
-        return d->fail(HQ_E_STATE, "hq_wire_add_batch: a device step holds < 2^31 messages");
+void hq_wire_dev_set_framing(hq_wire_dev *d, bool on, uint64_t deployment_id) {
+    d->framing = on;
+    d->deployment_id = deployment_id;
+}
+
+bool hq_wire_dev_framing(const hq_wire_dev *d) { return d->framing; }
+
+void hq_wire_dev_frame_stats(const hq_wire_dev *d, uint64_t out[4]) {
+    for (int k = 0; k < 4; ++k) out[k] = d->frame_stats[k];
+}
+
+// Where the device reads a batch: device memory as it is, pinned memory where the device maps it,
+// any other memory copied into the pinned staging
+static int place_batch(hq_wire_dev *d, const uint8_t *bytes, size_t len, const uint8_t **dev_out,
+                       const uint8_t **host_out = nullptr) {
     int rc = d->hip(hipSetDevice(d->ctx->device), "hipSetDevice");
     if (rc) return rc;
-    // device memory as it is, pinned memory where the device maps it
     const uint8_t *dev = static_cast<const uint8_t *>(hq::device_view(bytes));
-    if (!dev) {                                       // any other memory: into the pinned staging
+    if (host_out) *host_out = bytes;
+    if (!dev) {
         StageBlock *blk = nullptr;
         for (StageBlock &s : d->stage)
             if (s.cap - s.fill >= len + 16) blk = &s;
@@ -411,8 +439,33 @@ int hq_wire_dev_add_batch(hq_wire_dev *d, const uint8_t *bytes, size_t len, cons
         }
         std::memcpy(blk->host + blk->fill, bytes, len);
         dev = blk->dev + blk->fill;
+        if (host_out) *host_out = blk->host + blk->fill;   // (the caller's bytes may go)
         blk->fill += (len + 15) & ~size_t(15);
     }
+    *dev_out = dev;
+    return HQ_OK;
+}
+
+int hq_wire_dev_queue(hq_wire_dev *d, const uint8_t *bytes, size_t len, uint32_t index) {
+    const uint8_t *dev = nullptr, *host = nullptr;
+    if (len) {
+        const int rc = place_batch(d, bytes, len, &dev, &host);
+        if (rc) return rc;
+    }
+    d->batch_index.push_back(index);
+    d->batch_len.push_back(len);
+    d->refs.push_back(hq_wire_batch_ref{reinterpret_cast<uintptr_t>(dev), len});
+    d->host_bytes.push_back(host);                    // (should the step be framed here after all)
+    return HQ_OK;
+}
+
+int hq_wire_dev_add_batch(hq_wire_dev *d, const uint8_t *bytes, size_t len, const hq_wire_span *spans,
+                          uint64_t n_spans, uint64_t n_messages, uint32_t index) {
+    if (d->n_msgs + n_messages >= (1ull << 31))
+        return d->fail(HQ_E_STATE, "hq_wire_add_batch: a device step holds < 2^31 messages");
+    const uint8_t *dev = nullptr;
+    const int rc = place_batch(d, bytes, len, &dev);
+    if (rc) return rc;
     const uint32_t b = (uint32_t)d->batch_index.size();
     d->batch_index.push_back(index);
     d->batch_len.push_back(len);
@@ -427,20 +480,150 @@ int hq_wire_dev_add_batch(hq_wire_dev *d, const uint8_t *bytes, size_t len, cons
     return HQ_OK;
 }
 
+// one queued batch after hq_wire_frame_batch's verdict: counted, checked and its spans queued as
+// hq_wire.cpp's add_batch_device and hq_wire_dev_add_batch do
+static void queue_host_framed(hq_wire_dev *d, uint32_t b, const hq_wire_span *spans, uint64_t n_spans,
+                              const hq_wire_batch_info &bi, hq_wire_stats *add) {
+    add->batches++;
+    add->bytes += d->batch_len[b];
+    if (bi.deployment_id != d->deployment_id || bi.bin_ver != HQ_RPC_BIN_VERSION) {
+        add->dropped_batches++;
+        add->dropped_messages += bi.n_messages;
+        return;
+    }
+    for (uint64_t i = 0; i < n_spans; ++i) {
+        hq_wire_span s = spans[i];
+        s.offset += d->refs[b].offset;
+        s.first += (uint32_t)d->n_msgs;
+        d->spans.push_back(s);
+        d->span_batch.push_back(b);
+    }
+    d->n_msgs += bi.n_messages;
+}
+
+// The queued batches framed on the device: their spans in d_spans / d_span_batch (*on_device), the
+// results read back and applied. With a batch that came back unconfirmed or with spans that did
+// not fit, the whole step is framed here instead, into d->spans (arrival order stays).
+static int frame_queued(hq_wire_dev *d, hq_wire_stats *add, bool *on_device, uint64_t *n_spans) {
+    hq_ctx *ctx = d->ctx;
+    hipStream_t st = ctx->stream;
+    const uint64_t nb = d->refs.size();
+    const uint32_t S = HQ_WIRE_FRAME_SEGMENT, region = S / 128 + 8;
+    uint64_t segs = 0;
+    for (const hq_wire_batch_ref &r : d->refs) segs += (r.len + S - 1) / S;
+    const uint64_t span_cap = segs * region;          // (what the segments' regions hold)
+    const size_t o_results = 16, o_voids = o_results + nb * sizeof(hq_wire_frame_result),
+                 frame_bytes = o_voids + nb * 4;
+    d->spans.clear();
+    d->span_batch.clear();
+    d->n_msgs = 0;
+    d->frame_rejected.assign(nb, 0);
+    d->frame_stats[0] = segs;
+    d->frame_stats[1] = d->frame_stats[2] = 0;
+    *on_device = false;
+    *n_spans = 0;
+    if (!nb) return HQ_OK;
+    int rc = d->hip(hipSetDevice(ctx->device), "hipSetDevice");
+    if (!rc) rc = d->ensure(d->d_refs, nb * sizeof(hq_wire_batch_ref));
+    if (!rc) rc = d->ensure(d->d_frame, frame_bytes);
+    if (!rc) rc = d->ensure(d->d_spans, span_cap * sizeof(hq_wire_span));
+    if (!rc) rc = d->ensure(d->d_span_batch, span_cap * 4);
+    if (!rc && frame_bytes > d->h_frame_cap) {
+        if (d->h_frame) (void)hipHostFree(d->h_frame);
+        d->h_frame = nullptr;
+        d->h_frame_cap = 0;
+        rc = d->hip(hipHostMalloc(reinterpret_cast<void **>(&d->h_frame), 2 * frame_bytes,
+                                  hipHostMallocDefault), "hq_wire pinned readback");
+        if (!rc) d->h_frame_cap = 2 * frame_bytes;
+    }
+    if (!rc)
+        rc = d->hip(hipMemcpyAsync(d->d_refs.p, d->refs.data(), nb * sizeof(hq_wire_batch_ref),
+                                   hipMemcpyHostToDevice, st), "hq_wire H2D");
+    if (rc) return rc;
+    uint8_t *const f = static_cast<uint8_t *>(d->d_frame.p);
+    // the refs carry absolute addresses, so the buffer is all of memory
+    rc = hq_wire_frame_launch(ctx, nullptr, UINT64_MAX, static_cast<const hq_wire_batch_ref *>(d->d_refs.p),
+                              nb, S, segs, static_cast<hq_wire_span *>(d->d_spans.p), span_cap,
+                              static_cast<uint32_t *>(d->d_span_batch.p),
+                              reinterpret_cast<hq_wire_frame_result *>(f + o_results),
+                              reinterpret_cast<uint64_t *>(f), reinterpret_cast<uint32_t *>(f + o_voids),
+                              &d->deployment_id);
+    // one readback: the sort needs the step's size on the host
+    if (!rc) rc = hq::check_hip(ctx, hipMemcpyAsync(d->h_frame, f, frame_bytes, hipMemcpyDeviceToHost, st),
+                                "hq_wire D2H");
+    if (!rc) rc = hq::check_hip(ctx, hipStreamSynchronize(st), "hq_wire sync");
+    if (rc) return d->fail(rc, ctx->err);
+    const uint64_t *const totals = reinterpret_cast<const uint64_t *>(d->h_frame);
+    const hq_wire_frame_result *const res =
+        reinterpret_cast<const hq_wire_frame_result *>(d->h_frame + o_results);
+    const uint32_t *const voids = reinterpret_cast<const uint32_t *>(d->h_frame + o_voids);
+    for (uint64_t b = 0; b < nb; ++b) {
+        d->frame_stats[1] += voids[b];
+        d->frame_stats[2] += res[b].status >= 2;
+    }
+    if (d->frame_stats[2]) {                          // rare: framed here, as without the mode
+        d->frame_stats[3]++;
+        std::vector<hq_wire_span> spans(1024);
+        for (uint64_t b = 0; b < nb; ++b) {
+            hq_wire_batch_info bi;
+            uint64_t n = 0;
+            int frc = hq_wire_frame_batch(d->host_bytes[b], d->batch_len[b], 0, spans.data(), spans.size(),
+                                          &n, &bi);
+            if (frc == HQ_E_STATE) {
+                spans.resize(n);
+                frc = hq_wire_frame_batch(d->host_bytes[b], d->batch_len[b], 0, spans.data(), spans.size(),
+                                          &n, &bi);
+            }
+            if (frc) d->frame_rejected[b] = 1;
+            else queue_host_framed(d, (uint32_t)b, spans.data(), n, bi, add);
+        }
+        *n_spans = d->spans.size();
+        return HQ_OK;
+    }
+    for (uint64_t b = 0; b < nb; ++b) {
+        if (res[b].status) {
+            d->frame_rejected[b] = 1;
+            continue;
+        }
+        hq_wire_batch_info bi{};
+        bi.n_messages = res[b].n_messages;
+        bi.deployment_id = res[b].deployment_id;
+        bi.bin_ver = res[b].bin_ver;
+        queue_host_framed(d, (uint32_t)b, nullptr, 0, bi, add);
+    }
+    if (d->n_msgs != totals[0])
+        return d->fail(HQ_E_DEVICE, "hq_wire_step_device: the framing's totals differ from its results");
+    *on_device = true;
+    *n_spans = totals[1];
+    return HQ_OK;
+}
+
 int hq_wire_dev_step(hq_wire_dev *d, const hqs::WireEvent *locals, uint64_t n_locals,
                      hq_step_output *out, uint64_t counters[4], const uint32_t **rejected,
-                     uint64_t *n_rejected, uint64_t *rejected_bytes) {
+                     uint64_t *n_rejected, uint64_t *rejected_bytes, uint64_t *n_bad_message,
+                     hq_wire_stats *add) {
     hq_ctx *ctx = d->ctx;
     hipStream_t st = ctx->stream;
     std::memset(out, 0, sizeof *out);
     std::memset(counters, 0, 4 * sizeof(uint64_t));
+    *add = hq_wire_stats{};
     d->rejected.clear();
     *rejected = nullptr;
-    *n_rejected = *rejected_bytes = 0;
-    const uint64_t nm = d->n_msgs, N = nm + n_locals, nb = d->batch_index.size(),
-                   ns = d->spans.size();
+    *n_rejected = *rejected_bytes = *n_bad_message = 0;
+    int rc = HQ_OK;
+    bool spans_on_device = false;
+    uint64_t ns = d->spans.size();
+    if (d->framing) {
+        rc = frame_queued(d, add, &spans_on_device, &ns);
+        if (rc) return rc;
+        for (uint64_t b = 0; b < d->frame_rejected.size(); ++b)   // (should the step end early)
+            if (d->frame_rejected[b]) d->rejected.push_back(d->batch_index[b]);
+        *rejected = d->rejected.data();
+        *n_rejected = d->rejected.size();
+    }
+    const uint64_t nm = d->n_msgs, N = nm + n_locals, nb = d->batch_index.size();
     uint64_t G = 0;
-    int rc = hq_worker_group_count(d->worker, &G);
+    rc = hq_worker_group_count(d->worker, &G);
     if (rc) return d->fail(rc, "hq_wire_step_device: the worker's groups");
     if (N == 0 || G == 0) return HQ_OK;
     if (N >= (1ull << 31) || G >= (1ull << 30))
@@ -461,8 +644,8 @@ int hq_wire_dev_step(hq_wire_dev *d, const hqs::WireEvent *locals, uint64_t n_lo
                                                        vals_out, (int)N, 0, end_bit, st),
                     "hipcub sort size");
     if (!rc) rc = d->ensure(d->d_tmp, tmp);
-    if (!rc) rc = d->ensure(d->d_spans, ns * sizeof(hq_wire_span));
-    if (!rc) rc = d->ensure(d->d_span_batch, ns * 4);
+    if (!rc && !spans_on_device) rc = d->ensure(d->d_spans, ns * sizeof(hq_wire_span));
+    if (!rc && !spans_on_device) rc = d->ensure(d->d_span_batch, ns * 4);
     if (!rc) rc = d->ensure(d->d_bad, (nb + 1) * 4);
     if (!rc) rc = d->ensure(d->d_recs, N * sizeof(hqs::WireEvent));
     if (!rc) rc = d->ensure(d->d_cids, (nm + 1) * 8);
@@ -483,8 +666,10 @@ int hq_wire_dev_step(hq_wire_dev *d, const hqs::WireEvent *locals, uint64_t n_lo
         if (!rc && bytes)
             rc = d->hip(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st), "hq_wire H2D");
     };
-    h2d(d->d_spans.p, d->spans.data(), ns * sizeof(hq_wire_span));
-    h2d(d->d_span_batch.p, d->span_batch.data(), ns * 4);
+    if (!spans_on_device) {
+        h2d(d->d_spans.p, d->spans.data(), ns * sizeof(hq_wire_span));
+        h2d(d->d_span_batch.p, d->span_batch.data(), ns * 4);
+    }
     h2d(recs + nm, locals, n_locals * sizeof(hqs::WireEvent));
     if (!rc) rc = d->hip(hipMemsetAsync(d->d_bad.p, 0, (nb + 1) * 4, st), "memset");
     if (!rc) rc = d->hip(hipMemsetAsync(d->d_counters.p, 0, 64, st), "memset");
@@ -558,11 +743,16 @@ int hq_wire_dev_step(hq_wire_dev *d, const hqs::WireEvent *locals, uint64_t n_lo
     if (!rc) rc = hq::check_hip(ctx, hipStreamSynchronize(st), "hq_wire sync");
     if (rc) return d->fail(rc, ctx->err);
     for (int k = 0; k < 4; ++k) counters[k] = d->h_read[k];
-    for (uint64_t b = 0; b < nb; ++b)
-        if (d->h_bad[b]) {
+    d->rejected.clear();
+    for (uint64_t b = 0; b < nb; ++b) {
+        if (d->framing && d->frame_rejected[b]) {     // a framing error: counted nowhere
+            d->rejected.push_back(d->batch_index[b]);
+        } else if (d->h_bad[b]) {
             d->rejected.push_back(d->batch_index[b]);
             *rejected_bytes += d->batch_len[b];
+            ++*n_bad_message;
         }
+    }
     *rejected = d->rejected.data();
     *n_rejected = d->rejected.size();
     const uint64_t n_rows = d->h_read[4];

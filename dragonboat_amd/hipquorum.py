@@ -194,6 +194,12 @@ HQ_WIRE_SPAN_BYTES = 4096
 HQ_WIRE_SPAN_LARGE = 1
 WIRE_SPAN_DTYPE = np.dtype([("offset", "<u8"), ("len", "<u8"), ("first", "<u4"),
                             ("count", "<u2"), ("flags", "<u2")], align=True)
+# wire framing on the device: hq_wire_batch_ref, hq_wire_frame_result (hq_wire_frame_dev)
+HQ_WIRE_FRAME_SEGMENT = 65536
+WIRE_BATCH_REF_DTYPE = np.dtype([("offset", "<u8"), ("len", "<u8")], align=True)
+WIRE_FRAME_RESULT_DTYPE = np.dtype([("n_messages", "<u8"), ("n_spans", "<u8"),
+                                    ("deployment_id", "<u8"), ("source_address_len", "<u8"),
+                                    ("bin_ver", "<u4"), ("status", "<u4")], align=True)
 
 
 # leader heartbeat broadcast (include/hipquorum.h; hq_worker_heartbeats / hq_heartbeats_expand)
@@ -489,6 +495,10 @@ SIGNATURES = {
                                            ctypes.c_uint64, _u64p, ctypes.POINTER(WireBatchInfo)]),
     "hq_wire_decode_dev": (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, _vp, ctypes.c_uint64, _vp, _vp,
                                           ctypes.c_uint64]),
+    "hq_wire_frame_dev": (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, _vp, ctypes.c_uint64,
+                                         ctypes.c_uint32, _vp, ctypes.c_uint64, _vp, _vp, _vp]),
+    "hq_wire_set_device_framing": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "hq_wire_device_frame_stats": (ctypes.c_int, [_vp, _vp]),
     "hq_wire_attach_device": (ctypes.c_int, [_vp, _vp]),
     "hq_wire_step_device": (ctypes.c_int, [_vp, _vp, ctypes.POINTER(WireStats)]),
     "hq_wire_device_rejected": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), _u64p]),
@@ -2046,6 +2056,49 @@ def decode_dev(ctx: Context, data, spans, n_messages: int, data_len: Optional[in
             ctx.free(a)
 
 
+def frame_dev(ctx: Context, data, batches, segment_bytes: int = 0, span_cap: Optional[int] = None,
+              data_len: Optional[int] = None):
+    """hq_wire_frame_dev: the batches `batches` ((offset, len) pairs or a WIRE_BATCH_REF_DTYPE
+    array) of `data` (as decode_dev takes it) framed on the device. Returns (spans, span_batch,
+    results, totals): the dense WIRE_SPAN_DTYPE list of the batches with status 0 (as far as
+    span_cap, by default what cannot overflow), each span's batch, the WIRE_FRAME_RESULT_DTYPE
+    array and (messages, spans), copied back after the stream is drained."""
+    owned = []
+    if isinstance(data, (bytes, bytearray)):
+        data = np.frombuffer(bytes(data), np.uint8)
+    if isinstance(data, np.ndarray):
+        data_len = len(data) if data_len is None else data_len
+        if len(data) and pointer_kind(data) != HQ_PTR_PINNED_HOST:
+            data = ctx.upload(data)
+            owned.append(data)
+    elif isinstance(data, DeviceArray) and data_len is None:
+        data_len = data.count
+    refs = np.ascontiguousarray(np.array(batches, WIRE_BATCH_REF_DTYPE) if not isinstance(batches, np.ndarray)
+                                else batches, WIRE_BATCH_REF_DTYPE)
+    nb = len(refs)
+    S = segment_bytes or HQ_WIRE_FRAME_SEGMENT
+    if span_cap is None:
+        span_cap = int(sum((int(n) + S - 1) // S for n in refs["len"])) * (S // 128 + 8)
+    d_refs = ctx.upload(refs) if nb else None
+    d_spans = ctx.empty(max(1, span_cap), WIRE_SPAN_DTYPE)
+    d_sb = ctx.empty(max(1, span_cap), np.uint32)
+    d_res = ctx.empty(max(1, nb), WIRE_FRAME_RESULT_DTYPE)
+    d_tot = ctx.empty(2, np.uint64)
+    owned += [a for a in (d_refs, d_spans, d_sb, d_res, d_tot) if a is not None]
+    try:
+        ctx._check(lib.hq_wire_frame_dev(ctx.h, _p(data) if data_len else None, data_len or 0,
+                                         _p(d_refs) if nb else None, nb, segment_bytes, _p(d_spans),
+                                         span_cap, _p(d_sb), _p(d_res), _p(d_tot)))
+        totals = ctx.download(d_tot)
+        n = min(int(totals[1]), span_cap)
+        return (ctx.download(d_spans)[:n], ctx.download(d_sb)[:n], ctx.download(d_res)[:nb],
+                (int(totals[0]), int(totals[1])))
+    finally:
+        ctx.sync()
+        for a in owned:
+            ctx.free(a)
+
+
 def encode_wire_batch(msgs, deployment_id=0, source_address=b"", out=None):
     """hq_wire_encode_batch: one MessageBatch of WIRE_MESSAGE_DTYPE messages (no entries), as
     the sending node marshals it. Into `out` (uint8, e.g. pinned) when given: returns the bytes
@@ -2161,6 +2214,19 @@ class Wire:
         self._check(lib.hq_wire_attach_device(self.h, worker.h if worker else None),
                     "hq_wire_attach_device")
         self._dev_worker = worker
+
+    def set_device_framing(self, on: bool = True):
+        """hq_wire_set_device_framing: add_batch only queues the bytes; step_device frames them on
+        the device (and on the host after all when a batch comes back unconfirmed)."""
+        self._check(lib.hq_wire_set_device_framing(self.h, 1 if on else 0),
+                    "hq_wire_set_device_framing")
+
+    def device_frame_stats(self):
+        """hq_wire_device_frame_stats: (segments, void segments, batches with status 2 or 3) of
+        the last step_device, and the steps framed on the host since the attach."""
+        out = np.zeros(4, np.uint64)
+        self._check(lib.hq_wire_device_frame_stats(self.h, _p(out)), "hq_wire_device_frame_stats")
+        return tuple(int(x) for x in out)
 
     def step_device(self, copy=True):
         """hq_wire_step_device: (results as Worker.step returns them, WireStats). With copy=False

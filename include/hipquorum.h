@@ -1441,6 +1441,71 @@ int hq_wire_attach_device(hq_wire *w, hq_worker *worker);
 int hq_wire_step_device(hq_wire *w, hq_step_output *out, hq_wire_stats *stats);
 int hq_wire_device_rejected(hq_wire *w, const uint32_t **batches, uint64_t *n);
 
+/* ---------------------------------------------------------------- wire framing on the device -- */
+/*
+ * hq_wire_frame_batch's work on the GPU, so that the host touches a received batch once, to queue
+ * it. Additions to ABI 21 (new symbols only).
+ *
+ * A batch is cut every segment_bytes bytes; segment k owns the fields that start in
+ * [k S, (k + 1) S). One wave walks one segment: segment 0 from the batch's first byte, a later
+ * one from a GUESSED entry (the first position from which four `requests` headers follow one
+ * another, or from which at most eight valid fields end with the batch). No result depends on the
+ * guess: a second kernel walks each batch's segment records in order and takes a segment only
+ * when its entry is the exit of the one before, so every segment it takes was walked from its
+ * true entry; a segment that lies inside one long field is void. A batch with a segment whose
+ * guess was wrong comes back with status 3 and is framed by hq_wire_frame_batch instead.
+ *
+ * Spans are hq_wire_frame_batch's, closed at every segment's exit as well: a batch of one segment
+ * gives exactly its spans, a longer one spans that cover the same messages in the same order. A
+ * segment's spans are kept while they number at most segment_bytes / 128 + 8 (every segment whose
+ * spans close only by count or by bytes); beyond that, status 2.
+ */
+#define HQ_WIRE_FRAME_SEGMENT 65536u
+
+typedef struct hq_wire_batch_ref {
+    uint64_t offset, len;         /* one MessageBatch: bytes[offset .. offset + len) */
+} hq_wire_batch_ref;
+
+typedef struct hq_wire_frame_result {
+    uint64_t n_messages, n_spans, deployment_id, source_address_len;
+    uint32_t bin_ver;
+    uint32_t status;              /* 0 framed; 1 malformed (hq_wire_frame_batch: HQ_E_INVAL);
+                                     2 spans did not fit; 3 chain unconfirmed */
+} hq_wire_frame_result;
+
+/* Stateless; asynchronous on ctx's stream. bytes is device memory or pinned host memory the device
+ * reads in place; batches, spans, span_batch, results and totals are device memory. Frames
+ * batches[0 .. n_batches) (each within bytes[0 .. len), else status 1; batches that overlap so
+ * that their segments outnumber len / segment_bytes + n_batches may come back with status 3).
+ * results[b]: status 0 or 1 is hq_wire_frame_batch's verdict on the batch, and with status 0 the
+ * counts and fields are its *n_spans and *info (with status 1, 2 or 3 they are unspecified). The
+ * spans of the batches with status 0, in batch order, go to spans[0 .. min(totals[1], span_cap)),
+ * `offset` counted from bytes and `first` from the first message of the first such batch (what
+ * hq_wire_decode_dev takes), and their batch's number to span_batch (may be NULL);
+ * totals[0] = those batches' messages, totals[1] = their spans; a batch whose spans do not all
+ * lie below span_cap has status 2 and is still counted in both (a batch with status 2 for a
+ * segment's full region is not). segment_bytes: 0 for
+ * HQ_WIRE_FRAME_SEGMENT, else at least 64 (smaller: HQ_E_INVAL). Nothing outside a batch's bytes
+ * is read, and every loop is bounded by the batch's length. */
+int hq_wire_frame_dev(hq_ctx *ctx, const uint8_t *bytes, uint64_t len,
+                      const hq_wire_batch_ref *batches, uint64_t n_batches, uint32_t segment_bytes,
+                      hq_wire_span *spans, uint64_t span_cap, uint32_t *span_batch,
+                      hq_wire_frame_result *results, uint64_t totals[2]);
+
+/* The device mode of hq_wire (hq_wire_attach_device) with the framing on the device: on != 0,
+ * hq_wire_add_batch only queues the bytes (referenced in place or copied to the pinned staging as
+ * before) and returns HQ_OK for any bytes; hq_wire_step_device frames every queued batch on the
+ * device, reads the per-batch results back, applies the deployment-id and binary-version check to
+ * them, and goes on into the same decode, sort and step. A batch with a framing error is listed by
+ * hq_wire_device_rejected (in place of hq_wire_add_batch's HQ_E_INVAL) and counted nowhere. If any
+ * batch comes back with status 2 or 3 the whole step is framed on the host as without this mode.
+ * Outputs, *stats and the rejected list are those of the host-framed device mode given the same
+ * calls. HQ_E_STATE without a device worker attached, or with events queued. */
+int hq_wire_set_device_framing(hq_wire *w, int on);
+/* Of the last hq_wire_step_device: out[0] segments, out[1] void segments, out[2] batches with
+ * status 2 or 3; out[3] steps framed on the host because of such batches, since the attach. */
+int hq_wire_device_frame_stats(hq_wire *w, uint64_t out[4]);
+
 /* ---------------------------------------------------------------- leader heartbeat broadcast -- */
 /*
  * What a leader SENDS on a LeaderHeartbeat tick (handleLeaderHeartbeat, raft.go:1577-1579 ->

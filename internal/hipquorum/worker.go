@@ -669,3 +669,90 @@ func EncodeMany(jobs []Encode16Job, threads int) error {
 	}
 	return nil
 }
+
+// DeviceWire is the receiving side of a device worker (hq_wire_attach_device) with the framing on
+// the device (hq_wire_set_device_framing): the transport hands over each received MessageBatch as
+// it came, the host touches it once, to queue it, and Step frames, decodes, sorts and steps on the
+// GPU.
+type DeviceWire struct {
+	w   *C.hq_wire
+	x   *Worker
+	out *C.hq_step_output // C memory
+}
+
+// OpenDeviceWire binds a wire of deploymentID to the device worker x.
+func OpenDeviceWire(x *Worker, deploymentID uint64) (*DeviceWire, error) {
+	d := &DeviceWire{x: x}
+	if rc := C.hq_wire_open(C.uint64_t(deploymentID), &d.w); rc != C.HQ_OK {
+		return nil, fmt.Errorf("hq_wire_open: %d", int(rc))
+	}
+	rc := C.hq_wire_attach_device(d.w, x.w)
+	if rc == C.HQ_OK {
+		rc = C.hq_wire_set_device_framing(d.w, 1)
+	}
+	if rc != C.HQ_OK {
+		err := d.err(rc)
+		C.hq_wire_close(d.w)
+		return nil, err
+	}
+	d.out = (*C.hq_step_output)(C.calloc(1, C.size_t(unsafe.Sizeof(C.hq_step_output{}))))
+	return d, nil
+}
+
+func (d *DeviceWire) err(rc C.int) error {
+	if rc == C.HQ_OK {
+		return nil
+	}
+	return fmt.Errorf("hipquorum wire error %d: %s", int(rc), C.GoString(C.hq_wire_last_error(d.w)))
+}
+
+// Close frees the wire (not the worker).
+func (d *DeviceWire) Close() {
+	C.hq_wire_close(d.w)
+	C.free(unsafe.Pointer(d.out))
+	d.w, d.out = nil, nil
+}
+
+// Reset starts a step.
+func (d *DeviceWire) Reset() error { return d.err(C.hq_wire_reset(d.w)) }
+
+// AddBatch queues one received MessageBatch. Pinned C memory is read by the device in place and
+// must stay unchanged until Step returns; any other bytes are copied.
+func (d *DeviceWire) AddBatch(b []byte) error {
+	if len(b) == 0 {
+		return d.err(C.hq_wire_add_batch(d.w, nil, 0))
+	}
+	var pin runtime.Pinner
+	pin.Pin(&b[0])
+	defer pin.Unpin()
+	return d.err(C.hq_wire_add_batch(d.w, (*C.uint8_t)(unsafe.Pointer(&b[0])), C.size_t(len(b))))
+}
+
+// Step frames and decodes the queued batches on the device and steps the worker over them.
+func (d *DeviceWire) Step() (*Output, error) {
+	if rc := C.hq_wire_step_device(d.w, d.out, nil); rc != C.HQ_OK {
+		return nil, d.err(rc)
+	}
+	return &Output{c: d.out}, nil
+}
+
+// Rejected lists the batches of the last Step that were dropped whole, for a framing error or a
+// malformed message, as the indices of their AddBatch calls since Reset.
+func (d *DeviceWire) Rejected() ([]uint32, error) {
+	var p *C.uint32_t
+	var n C.uint64_t
+	if rc := C.hq_wire_device_rejected(d.w, &p, &n); rc != C.HQ_OK {
+		return nil, d.err(rc)
+	}
+	if n == 0 {
+		return nil, nil
+	}
+	return append([]uint32(nil), unsafe.Slice((*uint32)(unsafe.Pointer(p)), int(n))...), nil
+}
+
+// FrameStats is hq_wire_device_frame_stats: of the last Step the segments, the void segments and
+// the batches that came back unconfirmed; and the steps framed on the host since the attach.
+func (d *DeviceWire) FrameStats() (st [4]uint64, err error) {
+	err = d.err(C.hq_wire_device_frame_stats(d.w, (*C.uint64_t)(unsafe.Pointer(&st[0]))))
+	return st, err
+}

@@ -5,8 +5,10 @@ The workload is step5's steady-state mix built here (not bench.py's generator): 
 7 members (4 full members with the leader, a witness, 2 observers); per group and step a
 ReplicateResp and a HeartbeatResp from each of the 6 other members (12 messages), a proposal, and
 for every fourth group a local ReadIndex whose ctx the voting members' HeartbeatResps confirm. The
-messages arrive as one MessageBatch per (message type, sender), marshalled by hq_wire_encode_batch
-into pinned memory outside the timed region.
+messages arrive as one MessageBatch per (message type, sender), or with --batch-messages N cut
+into batches of N messages (2048 is the reference's SendQueueLength, which processMessages drains
+into one batch, transport.go:460-475), marshalled by hq_wire_encode_batch into pinned memory
+outside the timed region.
 
 Per step, over --steps steps after --warmup:
   host1   hq_wire_add_batch + add_locals + step_sized + hq_worker_step_stream, one thread
@@ -14,6 +16,9 @@ Per step, over --steps steps after --warmup:
           hq_worker_step_jobs
   device  hq_wire_attach_device: add_batch frames, hq_wire_step_device decodes, keys, sorts and
           steps on the GPU; the batches are read in place
+  device_framed  the same with hq_wire_set_device_framing: add_batch only queues, the step frames
+          on the GPU as well
+The device paths' host time is reported split into add_batch and add_locals.
 
 Every path must commit and release the same numbers of groups and ReadIndexes per step. The link
 yardstick is tools/link_probe's read rate on the same box. Output: one JSON line, and --out FILE.
@@ -57,11 +62,14 @@ class Arrivals:
     """Step s's batches for groups [lo, hi) in pinned buffers (rewritten per step), and its local
     events."""
 
-    def __init__(self, pin, cids):
+    def __init__(self, pin, cids, batch_messages=0):
         self.cids = cids
         n = len(cids)
-        self.bufs = [pin.pinned(n * 72 + 64, np.uint8) for _ in range(2 * (len(ROLES) - 1))]
-        self.lens = [0] * len(self.bufs)
+        self.chunk = batch_messages or max(1, n)
+        chunks = -(-n // self.chunk)
+        self.bufs = [pin.pinned(n * 72 + 64 * (chunks + 1), np.uint8)
+                     for _ in range(2 * (len(ROLES) - 1))]
+        self.batches = []                 # (address, length) of every batch, in arrival order
         self.msg = np.zeros(n, hq.WIRE_MESSAGE_DTYPE)
         self.msg["ev"]["kind"] = hq.EV_MESSAGE
         self.msg["ev"]["term"] = TERM
@@ -82,7 +90,7 @@ class Arrivals:
         self.lev["hint_high"][self.read_rows] = cids[self.reads]
 
     def set(self, s):
-        m, k = self.msg, 0
+        m, k, batches = self.msg, 0, []
         self.lev["hint"][self.read_rows] = s + 1
         for typ in (RREP, HBRESP):
             for node in range(2, len(ROLES) + 1):
@@ -92,14 +100,22 @@ class Arrivals:
                 if typ == HBRESP and ROLES[node - 1] != OBSERVER:   # (an observer's ack of a ctx
                     m["ev"]["hint"][self.reads] = s + 1             # is the worker's fallback)
                     m["ev"]["hint_high"][self.reads] = self.cids[self.reads]
-                out = hq.encode_wire_batch(m, deployment_id=DEP, source_address=b"n%d:63000" % node,
-                                           out=self.bufs[k])
-                self.lens[k] = len(out)
+                at = 0
+                for lo in range(0, len(m), self.chunk):
+                    out = hq.encode_wire_batch(m[lo:lo + self.chunk], deployment_id=DEP,
+                                               source_address=b"n%d:63000" % node,
+                                               out=self.bufs[k][at:])
+                    batches.append((self.bufs[k].ctypes.data + at, len(out)))
+                    at += len(out)
                 k += 1
+        self.batches = batches
+
+    def add_batches_to(self, wire):
+        for addr, n in self.batches:
+            wire.add_batch_at(addr, n)
 
     def add_to(self, wire):
-        for b, n in zip(self.bufs, self.lens):
-            wire.add_batch_at(b.ctypes.data, n)
+        self.add_batches_to(wire)
         wire.add_locals(self.cids, self.loff, self.lev)
 
     @property
@@ -108,7 +124,7 @@ class Arrivals:
 
     @property
     def n_bytes(self):
-        return sum(self.lens)
+        return sum(n for _, n in self.batches)
 
 
 def counts(res):
@@ -135,6 +151,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--threads", type=int, default=16)
+    ap.add_argument("--batch-messages", type=int, default=0,
+                    help="cut each sender's traffic into batches of N messages (0: one batch)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     G, W = a.groups, a.threads
@@ -150,8 +168,8 @@ def main():
         w.add_groups(g[lo:hi], m[nm * lo:nm * hi])
         return w
 
-    arr = Arrivals(pin, cids)
-    parts = [Arrivals(pin, cids[bounds[i]:bounds[i + 1]]) for i in range(W)]
+    arr = Arrivals(pin, cids, a.batch_messages)
+    parts = [Arrivals(pin, cids[bounds[i]:bounds[i + 1]], a.batch_messages) for i in range(W)]
     # host, one thread
     w1, wire1 = worker(0, G), hq.Wire(DEP)
     wire1.attach(w1)
@@ -168,9 +186,15 @@ def main():
     # device mode
     wd, wired = worker(0, G), hq.Wire(DEP)
     wired.attach_device(wd)
+    wf, wiref = worker(0, G), hq.Wire(DEP)
+    wiref.attach_device(wf)
+    wiref.set_device_framing(True)
 
     t = {"host1": [], "host1_decode": [], "host16": [], "host16_decode": [], "device": [],
-         "device_frame": [], "device_step_gpu": []}
+         "device_frame": [], "device_add_batch": [], "device_add_locals": [], "device_step": [],
+         "device_step_gpu": [], "device_framed": [], "device_framed_add_batch": [],
+         "device_framed_add_locals": [], "device_framed_step": [], "device_framed_step_gpu": []}
+    frame_stats = None
     same = True
     for s in range(a.warmup + a.steps):
         arr.set(s)
@@ -200,13 +224,28 @@ def main():
 
         t6 = time.perf_counter()
         wired.reset()
-        arr.add_to(wired)
+        arr.add_batches_to(wired)
+        t6b = time.perf_counter()
+        wired.add_locals(arr.cids, arr.loff, arr.lev)
         t7 = time.perf_counter()
         rd, std = wired.step_device(copy=False)
         t8 = time.perf_counter()
         cd = counts(rd)
-        same = same and c1 == c16 == cd and c1[2] == 0 and \
-            all(getattr(st1, k) == getattr(std, k) for k, _ in hq.WireStats._fields_)
+        gpu_d = rd["gpu_ns"] * 1e-9
+
+        t9 = time.perf_counter()
+        wiref.reset()
+        arr.add_batches_to(wiref)
+        t9b = time.perf_counter()
+        wiref.add_locals(arr.cids, arr.loff, arr.lev)
+        t10 = time.perf_counter()
+        rf, stf = wiref.step_device(copy=False)
+        t11 = time.perf_counter()
+        cf = counts(rf)
+        frame_stats = wiref.device_frame_stats()
+        same = same and c1 == c16 == cd == cf and c1[2] == 0 and \
+            all(getattr(st1, k) == getattr(std, k) == getattr(stf, k)
+                for k, _ in hq.WireStats._fields_)
         if s >= a.warmup:
             t["host1"].append(t2 - t0)
             t["host1_decode"].append(t1 - t0)
@@ -214,13 +253,24 @@ def main():
             t["host16_decode"].append(t4 - t3)
             t["device"].append(t8 - t6)
             t["device_frame"].append(t7 - t6)
-            t["device_step_gpu"].append(rd["gpu_ns"] * 1e-9)
+            t["device_add_batch"].append(t6b - t6)
+            t["device_add_locals"].append(t7 - t6b)
+            t["device_step"].append(t8 - t7)
+            t["device_step_gpu"].append(gpu_d)
+            t["device_framed"].append(t11 - t9)
+            t["device_framed_add_batch"].append(t9b - t9)
+            t["device_framed_add_locals"].append(t10 - t9b)
+            t["device_framed_step"].append(t11 - t10)
+            t["device_framed_step_gpu"].append(rf["gpu_ns"] * 1e-9)
     n_spans = -(-arr.n_messages // 64)            # (an estimate from below: spans also end at 4 KiB)
     ms = lambda v: {"median": float(np.median(v)) * 1e3, "worst": float(np.max(v)) * 1e3}
     link = link_read_gbps(a.device)
     rec = {"tool": "wire_dev_probe", "groups": G, "steps": a.steps, "warmup": a.warmup,
            "messages_per_step": arr.n_messages, "local_events_per_step": len(arr.lev),
-           "message_bytes_per_step": arr.n_bytes,
+           "message_bytes_per_step": arr.n_bytes, "batch_messages": a.batch_messages,
+           "batches_per_step": len(arr.batches),
+           "frame_stats_last_step": dict(zip(("segments", "void_segments", "open_batches",
+                                              "steps_framed_on_host"), frame_stats or ())),
            "bytes_per_message": arr.n_bytes / arr.n_messages,
            "span_index_bytes_per_step_min": n_spans * hq.WIRE_SPAN_DTYPE.itemsize,
            "commits_ready_fallback_last_step": c1, "paths_agree": bool(same),
@@ -234,7 +284,7 @@ def main():
         with open(a.out, "w") as f:
             f.write(line + "\n")
     pool.shutdown()
-    for x in [wire1, wired] + wires + [w1, wd] + wk:
+    for x in [wire1, wired, wiref] + wires + [w1, wd, wf] + wk:
         x.close()
     pin.close()
     return 0 if same else 1
