@@ -113,6 +113,21 @@ struct hq_dstate_view {
     uint64_t n_groups;                // group records uploaded (valid handles)
 };
 void hq_dstep_view(hq_dstep *d, hq_dstate_view *out);
+// the same state for a kernel that edits it between steps on ctx's stream (hq_config.hip)
+struct hq_dstate_mut {
+    hq_ctx *ctx;
+    hq_dgroup *groups;
+    hq_dread *reads;
+    hq_dmember *members;
+    uint64_t n_groups;
+};
+void hq_dstep_view_mut(hq_dstep *d, hq_dstate_mut *out);
+// member records [m0, total) reserved at the pool's end, zeroed (the member arrays grown to hold
+// `total` records; the records below m0 keep their contents)
+int hq_dstep_reserve_members(hq_dstep *d, uint64_t m0, uint64_t total);
+// a group edited on the device may now have n members: the step's kernels are chosen by the most
+// members of any group (8 member slots in registers, or kDMembers)
+void hq_dstep_raise_max_members(hq_dstep *d, uint32_t n);
 // one step over the device state; the kernels check the input (out->input_error)
 int hq_dstep_run(hq_dstep *d, const hq_dstep_in *in, hq_dstep_out *out);
 // several engines' steps through shared launches (hq_worker_step_jobs): every input a sized

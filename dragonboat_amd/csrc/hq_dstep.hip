@@ -2004,6 +2004,32 @@ void hq_dstep_view(hq_dstep *d, hq_dstate_view *out) {
     *out = hq_dstate_view{d->ctx, d->groups, d->reads, d->members, d->n_groups};
 }
 
+void hq_dstep_view_mut(hq_dstep *d, hq_dstate_mut *out) {
+    *out = hq_dstate_mut{d->ctx, d->groups, d->reads, d->members, d->n_groups};
+}
+
+int hq_dstep_reserve_members(hq_dstep *d, uint64_t m0, uint64_t total) {
+    hq_ctx *ctx = d->ctx;
+    int rc = hq::check_hip(ctx, hipSetDevice(ctx->device), "hipSetDevice");
+    if (!rc && total > d->mcap) {
+        size_t mc = d->mcap * sizeof(hq_dmember), xn = d->mcap * 8;
+        rc = grow(ctx, reinterpret_cast<void **>(&d->members), &mc, total * sizeof(hq_dmember), true,
+                  "hq_dstep members");
+        if (!rc)
+            rc = grow(ctx, reinterpret_cast<void **>(&d->match_old), &xn, total * 8, false,
+                      "hq_dstep saved matches");
+        if (!rc) d->mcap = std::min(mc / sizeof(hq_dmember), xn / 8);
+    }
+    if (!rc && total > m0)
+        rc = hq::check_hip(ctx, hipMemsetAsync(d->members + m0, 0, (total - m0) * sizeof(hq_dmember),
+                                               ctx->stream), "hq_dstep members");
+    return rc;
+}
+
+void hq_dstep_raise_max_members(hq_dstep *d, uint32_t n) {
+    if (n > d->max_members) d->max_members = n;
+}
+
 namespace {
 
 // One worker's step from its preparation to its outputs (hq_dstep_run; hq_dstep_run_jobs runs

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "../../include/hipquorum.h"
+#include "hq_config.h"
 #include "hq_dstep.h"
 #include "hq_heartbeat.h"
 #include "hq_heartbeat_wire.h"
@@ -116,6 +117,14 @@ struct hq_worker {
     std::vector<hq_heartbeat_batch> hbw_batches;
     std::vector<hb_fields> hbw_msgs;
     std::vector<uint64_t> hbw_first;
+    // hq_worker_config_changes: a device worker's buffers (first call), the call's descriptors
+    // and its output (a host worker's status column; the commit records of both)
+    hq_cfg_dev *cfg = nullptr;
+    std::vector<hq_cfg_desc> cc_desc;
+    std::vector<uint8_t> cc_cap;          // a moving group's new member range
+    std::vector<uint32_t> cc_status;
+    std::vector<hq_commit_event> cc_commits;
+    uint64_t readbacks = 0;               // sync_from_device calls that copied the state back
     std::vector<hq_event> decoded;        // host worker: a stream step's rows
     std::vector<uint64_t> sized_off, sized_boff;   // host worker: a sized stream's prefixes
     std::vector<uint32_t> sized_groups;            // and its implicit handles
@@ -187,6 +196,9 @@ struct hq_worker {
     int heartbeats(uint64_t n, const uint32_t *list, hq_heartbeat_output *out);
     int heartbeat_batches(uint64_t n, const uint32_t *list, const hq_heartbeat_wire_config *cfg,
                           hq_heartbeat_batches *out);
+    int config_desc(const Group &g, const hq_config_change &c, uint32_t limit, hq_cfg_desc &d);
+    void config_edit(Group &g, uint32_t h, const hq_cfg_desc &d, uint8_t new_cap);
+    int config_changes(uint64_t n, const hq_config_change *ch, hq_config_output *out);
     Verdict handle(Group &g, const hq_event &e, uint64_t ei);
     Verdict read_index(Group &g, uint64_t from, uint64_t low, uint64_t high, uint64_t ei);
     void advance(Group &g);
@@ -848,6 +860,7 @@ int hq_worker::sync_to_device() {
 // the whole device state back into the host records
 int hq_worker::sync_from_device() {
     if (!host_stale) return HQ_OK;
+    ++readbacks;
     const uint64_t G = dev_groups, M = dev_members;
     std::vector<hq_dgroup> dg(G);
     std::vector<hq_dread> dr(G * kDReads);
@@ -1160,8 +1173,314 @@ int hq_worker::heartbeat_batches(uint64_t n, const uint32_t *list, const hq_hear
     return HQ_OK;
 }
 
+// ------------------------------------------------------------------------------ membership ---
+// handleNodeConfigChange (raft.go:1540-1559) for the listed groups. The structure of a group —
+// member ids, roles, positions — is the host's own even while a device worker's mirror is stale,
+// so every change becomes a descriptor here (hq_config.h); a device worker's are applied where
+// the state lives (hq_config.hip), a host worker's below, and the same structural edit then goes
+// into the host records of both.
+
+// One change as a descriptor, from the group's structure alone. HQ_E_INVAL for what the reference
+// panics on.
+int hq_worker::config_desc(const Group &g, const hq_config_change &c, uint32_t limit, hq_cfg_desc &d) {
+    d = hq_cfg_desc{};
+    d.node_id = c.node_id;
+    d.group = c.group;
+    d.new_mem = kCfgNoMove;
+    d.kind = kCfgNoop;
+    d.slot = kCfgNoSlot;
+    d.n_members = g.n_members;
+    d.n_voting = g.n_voting;
+    const Member *m = pool.data() + g.mem;
+    hq_cfg_layout l{0, g.n_voting, g.n_members};
+    while (l.n_remotes < g.n_voting && m[l.n_remotes].role == HQ_ROLE_REMOTE) ++l.n_remotes;
+    const int mi = member_of(g, c.node_id);
+    const uint32_t role = mi >= 0 ? m[mi].role : 0xFFu;
+    uint32_t new_role = HQ_ROLE_REMOTE;
+    switch (c.type) {
+    case HQ_CC_REMOVE_NODE:
+        if (mi < 0) {
+            d.kind = kCfgCommitOnly;                // removeNode's tryCommit runs all the same
+        } else if (mi == 0) {
+            d.kind = kCfgFallback;                  // the node itself: dragonboat stops it
+        } else {
+            d.kind = kCfgRemove;
+            d.src = (uint8_t)mi;
+            d.slot = (uint8_t)cfg_remove_slot((uint32_t)mi, l);
+            d.order = m[mi].order;
+        }
+        return HQ_OK;
+    case HQ_CC_ADD_NODE:
+        if (role == HQ_ROLE_REMOTE) return HQ_OK;   // already a voting member (raft.go:1141-1144)
+        if (role == HQ_ROLE_WITNESS)
+            return fail(HQ_E_INVAL, "hq_worker_config_changes: ADD_NODE of a witness (the reference "
+                                    "panics: could not promote witness to a full member)");
+        if (role == HQ_ROLE_OBSERVER) {             // promoted with its progress (raft.go:1145-1148)
+            if (g.n_voting + 1u > n_max) {
+                d.kind = kCfgFallback;
+                return HQ_OK;
+            }
+            d.kind = kCfgPromote;
+            d.src = (uint8_t)mi;
+            d.dst = d.slot = (uint8_t)cfg_promote_pos(l);
+            return HQ_OK;
+        }
+        break;
+    case HQ_CC_ADD_OBSERVER:
+    case HQ_CC_ADD_WITNESS:
+        new_role = c.type == HQ_CC_ADD_OBSERVER ? HQ_ROLE_OBSERVER : HQ_ROLE_WITNESS;
+        if (role == new_role) return HQ_OK;
+        if (mi >= 0)
+            return fail(HQ_E_INVAL, "hq_worker_config_changes: ADD_OBSERVER / ADD_WITNESS of a member "
+                                    "in another role");
+        break;
+    default:
+        return fail(HQ_E_INVAL, "hq_worker_config_changes: unknown change type");
+    }
+    // a new member, match 0 and inactive (setRemote / setObserver / setWitness(nodeID, 0, ...))
+    if (g.n_members + 1u > limit || (new_role != HQ_ROLE_OBSERVER && g.n_voting + 1u > n_max)) {
+        d.kind = kCfgFallback;
+        return HQ_OK;
+    }
+    d.kind = kCfgInsert;
+    d.dst = (uint8_t)cfg_insert_pos(c.type, l);
+    d.slot = (uint8_t)cfg_insert_slot(c.type, l);
+    d.role = (uint8_t)new_role;
+    d.order = g.n_members;
+    return HQ_OK;
+}
+
+// The structural edit of an applied change in the host records (a host worker's state; a device
+// worker's mirror, index-identical with the device pool), and the group's row of the route column.
+void hq_worker::config_edit(Group &g, uint32_t h, const hq_cfg_desc &d, uint8_t new_cap) {
+    Member *m = members(g);
+    const uint32_t n = g.n_members;
+    const bool rm = d.kind == kCfgRemove;
+    if (rm) {
+        for (uint32_t j = d.src; j + 1 < n; ++j) m[j] = m[j + 1];
+        for (uint32_t j = 0; j + 1 < n; ++j)
+            m[j].order = (uint8_t)cfg_order_after_remove(m[j].order, d.order);
+        g.n_members = (uint8_t)(n - 1);
+    } else if (d.kind == kCfgInsert) {
+        const Member fresh{d.node_id, 0, d.role, 0, d.order, {0, 0, 0, 0, 0}};
+        if (d.new_mem != kCfgNoMove) {
+            Member *nm = pool.data() + d.new_mem;
+            for (uint32_t j = 0; j < n; ++j) nm[cfg_pos_after_insert(j, d.dst)] = m[j];
+            nm[d.dst] = fresh;
+            g.mem = d.new_mem;
+            g.mem_cap = new_cap;
+        } else {
+            for (uint32_t j = n; j > d.dst; --j) m[j] = m[j - 1];
+            m[d.dst] = fresh;
+        }
+        g.n_members = (uint8_t)(n + 1);
+    } else {                                        // kCfgPromote
+        Member carry = m[d.src];
+        for (uint32_t j = d.src; j > d.dst; --j) m[j] = m[j - 1];
+        carry.role = HQ_ROLE_REMOTE;
+        m[d.dst] = carry;
+    }
+    if (d.slot != kCfgNoSlot) {                     // the slot bitmaps follow the voting slots
+        const uint32_t s = d.slot;
+        auto remap = [&](uint8_t b) {
+            return (uint8_t)(rm ? cfg_remove_bit(b, s) : cfg_insert_bit(b, s));
+        };
+        g.granted = remap(g.granted);
+        g.rejected = remap(g.rejected);
+        if (ReadQueue *q = reads(g))
+            for (uint32_t k = 0; k < q->n; ++k) {
+                ReadStatus &r = q->r[k];
+                r.confirmed = remap(r.confirmed);
+                if (rm) {
+                    for (uint32_t v = s; v + 1 < HQ_MAX_VOTERS; ++v) r.ord[v] = r.ord[v + 1];
+                    r.ord[HQ_MAX_VOTERS - 1] = kNoAck;
+                } else {
+                    for (uint32_t v = HQ_MAX_VOTERS - 1; v > s; --v) r.ord[v] = r.ord[v - 1];
+                    r.ord[s] = kNoAck;
+                }
+            }
+        g.n_voting = (uint8_t)(rm ? g.n_voting - 1 : g.n_voting + 1);
+    }
+    // the route column's row moves with the member list
+    if (d.kind == kCfgPromote || routes.size() < ((size_t)h + 1) * kDMembers) return;
+    uint16_t *row = routes.data() + (size_t)h * kDMembers;
+    if (rm) {
+        const uint32_t end = std::min<uint32_t>(n, kDMembers);
+        for (uint32_t j = d.order; j + 1 < end; ++j) row[j] = row[j + 1];
+        if (d.order < end) row[end - 1] = (uint16_t)HQ_ROUTE_NONE;
+    } else if (d.order < kDMembers) {
+        row[d.order] = (uint16_t)HQ_ROUTE_NONE;
+    }
+    if (routes_lo == routes_hi) {
+        routes_lo = h;
+        routes_hi = (uint64_t)h + 1;
+    } else {
+        routes_lo = std::min<uint64_t>(routes_lo, h);
+        routes_hi = std::max<uint64_t>(routes_hi, (uint64_t)h + 1);
+    }
+}
+
+int hq_worker::config_changes(uint64_t n, const hq_config_change *ch, hq_config_output *out) {
+    const uint32_t limit = dstep ? kDMembers : 64;
+    // every check first: a refused list changes nothing
+    cc_desc.resize(n);
+    int rc = HQ_OK;
+    uint64_t marked = 0;
+    for (; marked < n && !rc; ++marked) {
+        const hq_config_change &c = ch[marked];
+        if (c.group >= groups.size()) rc = fail(HQ_E_INVAL, "hq_worker_config_changes: unknown group handle");
+        else if (groups[c.group].has(kTouched)) rc = fail(HQ_E_INVAL, "hq_worker_config_changes: a group is listed twice");
+        else if (c.type > HQ_CC_ADD_WITNESS) rc = fail(HQ_E_INVAL, "hq_worker_config_changes: unknown change type");
+        else if (c.node_id == 0) rc = fail(HQ_E_INVAL, "hq_worker_config_changes: node_id 0");
+        else rc = config_desc(groups[c.group], c, limit, cc_desc[marked]);
+        if (rc) break;
+        groups[c.group].set(kTouched);
+    }
+    for (uint64_t i = 0; i < marked; ++i) groups[ch[i].group].clear(kTouched);
+    if (rc) return rc;
+
+    cc_cap.assign(n, 0);
+    cc_commits.clear();
+    // a full member range moves to the pool's end (with room for one more change)
+    auto move_out = [&](uint64_t i) {
+        hq_cfg_desc &d = cc_desc[i];
+        const Group &g = groups[d.group];
+        if (d.kind != kCfgInsert || g.mem_cap > g.n_members) return;
+        cc_cap[i] = (uint8_t)std::min<uint32_t>(limit, g.n_members + 2u);
+        d.new_mem = (uint32_t)pool.size();
+        pool.resize(pool.size() + cc_cap[i]);
+    };
+    const uint32_t *status = nullptr;
+    const uint64_t *committed = nullptr;
+    uint64_t gpu_ns = 0;
+    if (dstep) {
+        rc = sync_to_device();                      // pending add / set_group first, as a step does
+        if (rc) return rc;
+        uint32_t most = 0;
+        for (uint64_t i = 0; i < n; ++i) {
+            if (pool.size() + limit > UINT32_MAX) return fail(HQ_E_NOMEM, "hq_worker_config_changes: member pool full");
+            move_out(i);
+            if (cc_desc[i].kind == kCfgInsert) most = std::max<uint32_t>(most, cc_desc[i].n_members + 1u);
+        }
+        // the device pool stays index-identical with the host's: the reserved records exist there
+        // before the kernel writes them and are never uploaded from the mirror
+        rc = hq(hq_dstep_reserve_members(dstep, dev_members, pool.size()), "hq_worker_config_changes");
+        if (rc) {
+            pool.resize(dev_members);
+            return rc;
+        }
+        dev_members = pool.size();
+        hq_dstep_raise_max_members(dstep, most);    // the step's 8-slot kernels must not see 9 members
+        if (!cfg && (rc = hq(hq_cfg_dev_open(ctx, &cfg), "hq_worker_config_changes"))) return rc;
+        hq_dstate_mut st;
+        hq_dstep_view_mut(dstep, &st);
+        uint32_t e = 0;
+        rc = hq_cfg_dev_run(cfg, &st, dev_members, n, cc_desc.data(), &status, &committed, &gpu_ns, &e);
+        if (rc == HQ_E_INVAL && e)
+            return fail(HQ_E_STATE, "hq_worker_config_changes: a resident group record does not match "
+                                    "the host's (internal)");
+        if ((rc = hq(rc, "hq_worker_config_changes"))) return rc;
+    } else {
+        // a host worker decides from its own records what the kernel decides from the resident ones
+        cc_status.resize(n);
+        for (uint64_t i = 0; i < n; ++i) {
+            const hq_cfg_desc &d = cc_desc[i];
+            const Group &g = groups[d.group];
+            uint32_t s = HQ_CC_NOOP;
+            if (g.has(kSuspended)) {
+                s = HQ_CC_SUSPENDED;
+            } else if (d.kind == kCfgFallback) {
+                s = HQ_CC_FALLBACK;
+            } else if (d.kind >= kCfgRemove) {
+                s = HQ_CC_APPLIED;
+                if (d.kind == kCfgRemove && d.slot != kCfgNoSlot) {
+                    uint32_t bits = g.granted | g.rejected;
+                    if (const ReadQueue *q = g.rq == kNone ? nullptr : &rqs[g.rq])
+                        for (uint32_t k = 0; k < q->n; ++k) {
+                            bits |= q->r[k].confirmed;
+                            for (uint32_t v = 0; v < HQ_MAX_VOTERS; ++v)
+                                if (q->r[k].ord[v] != kNoAck) bits |= 1u << v;
+                        }
+                    if ((bits >> d.slot) & 1) s = HQ_CC_FALLBACK;
+                }
+            }
+            cc_status[i] = s;
+            if (s == HQ_CC_APPLIED) {
+                if (pool.size() + limit > UINT32_MAX) return fail(HQ_E_NOMEM, "hq_worker_config_changes: member pool full");
+                move_out(i);
+            }
+        }
+        status = cc_status.data();
+    }
+
+    // the same edit in the host records; a host worker's tryCommit through its commit pass
+    l_commit.clear();
+    l_ri.clear();
+    l_vote.clear();
+    l_cq.clear();
+    uint64_t counts[4] = {0, 0, 0, 0};
+    for (uint64_t i = 0; i < n; ++i) {
+        const hq_cfg_desc &d = cc_desc[i];
+        Group &g = groups[d.group];
+        const uint32_t s = status[i] <= HQ_CC_SUSPENDED ? status[i] : HQ_CC_SUSPENDED;
+        ++counts[s];
+        if (s == HQ_CC_FALLBACK) g.set(kSuspended);
+        if (s == HQ_CC_APPLIED) config_edit(g, d.group, d, cc_cap[i]);
+        const bool removal = d.kind == kCfgRemove || d.kind == kCfgCommitOnly;
+        if (dstep) {
+            if (committed[i]) {
+                g.committed = committed[i];
+                cc_commits.push_back({g.cluster_id, committed[i]});
+            }
+        } else if (removal && s <= HQ_CC_NOOP && g.state == HQ_STATE_LEADER) {
+            g.committed0 = g.committed;             // removeNode's tryCommit (raft.go:1194-1198)
+            g.set(kCommitDue);
+            l_commit.push_back(d.group);
+        }
+    }
+    if (!l_commit.empty()) {
+        rc = run_pass();
+        for (uint32_t gi : l_commit) groups[gi].clear(kCommitDue);
+        if (rc) return rc;
+        for (uint32_t gi : l_commit) {
+            const Group &g = groups[gi];
+            if (g.committed != g.committed0) cc_commits.push_back({g.cluster_id, g.committed});
+        }
+    }
+    out->status = status;
+    out->commits = cc_commits.data();
+    out->n_commits = cc_commits.size();
+    out->n_applied = counts[HQ_CC_APPLIED];
+    out->n_noop = counts[HQ_CC_NOOP];
+    out->n_fallback = counts[HQ_CC_FALLBACK];
+    out->n_suspended = counts[HQ_CC_SUSPENDED];
+    out->gpu_ns = gpu_ns;
+    return HQ_OK;
+}
+
 // ------------------------------------------------------------------------------ C-ABI ------
 extern "C" {
+
+int hq_worker_config_changes(hq_worker *w, uint64_t n, const hq_config_change *changes,
+                             hq_config_output *out) {
+    if (!w) return HQ_E_INVAL;
+    try {
+        if (!out || (n && !changes))
+            return w->fail(HQ_E_INVAL, "hq_worker_config_changes: NULL argument");
+        if (n > UINT32_MAX) return w->fail(HQ_E_INVAL, "hq_worker_config_changes: a group is listed twice");
+        std::memset(out, 0, sizeof *out);
+        if (n == 0) return HQ_OK;
+        return w->config_changes(n, changes, out);
+    } catch (const std::bad_alloc &) {
+        return w->fail(HQ_E_NOMEM, "hq_worker_config_changes: out of memory");
+    }
+}
+
+int hq_worker_readback_count(hq_worker *w, uint64_t *n) {
+    if (!w || !n) return HQ_E_INVAL;
+    *n = w->readbacks;
+    return HQ_OK;
+}
 
 int hq_worker_set_heartbeat_routes(hq_worker *w, uint32_t first_handle, uint64_t n_groups,
                                    const uint16_t *routes) {
@@ -1313,6 +1632,7 @@ void hq_worker_close(hq_worker *w) {
     if (!w) return;
     if (w->hb) hq_hb_dev_close(w->hb);
     if (w->hbw) hq_hbw_dev_close(w->hbw);
+    if (w->cfg) hq_cfg_dev_close(w->cfg);
     if (w->dstep) hq_dstep_close(w->dstep);
     if (w->ctx) {
         hq_sync(w->ctx);

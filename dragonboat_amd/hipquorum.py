@@ -241,6 +241,22 @@ class HeartbeatBatches(ctypes.Structure):
                 ("n_unrouted", ctypes.c_uint64), ("gpu_ns", ctypes.c_uint64)]
 
 
+# membership changes (hq_worker_config_changes)
+HQ_CC_ADD_NODE, HQ_CC_REMOVE_NODE, HQ_CC_ADD_OBSERVER, HQ_CC_ADD_WITNESS = 0, 1, 2, 3
+HQ_CC_APPLIED, HQ_CC_NOOP, HQ_CC_FALLBACK, HQ_CC_SUSPENDED = 0, 1, 2, 3
+CONFIG_CHANGE_DTYPE = np.dtype([("group", "<u4"), ("type", "<u4"), ("node_id", "<u8")], align=True)
+assert CONFIG_CHANGE_DTYPE.itemsize == 16
+
+
+class ConfigOutput(ctypes.Structure):
+    """Mirror of ``hq_config_output``."""
+
+    _fields_ = [("status", _vp), ("commits", _vp), ("n_commits", ctypes.c_uint64),
+                ("n_applied", ctypes.c_uint64), ("n_noop", ctypes.c_uint64),
+                ("n_fallback", ctypes.c_uint64), ("n_suspended", ctypes.c_uint64),
+                ("gpu_ns", ctypes.c_uint64)]
+
+
 class WireBatchInfo(ctypes.Structure):
     _fields_ = [("n_messages", ctypes.c_uint64), ("deployment_id", ctypes.c_uint64),
                 ("source_address_len", ctypes.c_uint64), ("bin_ver", ctypes.c_uint32),
@@ -511,6 +527,9 @@ SIGNATURES = {
                                                    ctypes.POINTER(HeartbeatBatches)]),
     "hq_heartbeats_expand": (ctypes.c_int, [ctypes.POINTER(HeartbeatOutput), _vp, _vp, _vp, _vp,
                                             _vp, _vp, ctypes.c_uint64, _u64p]),
+    "hq_worker_config_changes": (ctypes.c_int, [_vp, ctypes.c_uint64, _vp,
+                                                ctypes.POINTER(ConfigOutput)]),
+    "hq_worker_readback_count": (ctypes.c_int, [_vp, _u64p]),
     "hq_synth_commit_dev": (ctypes.c_int, [_vp, ctypes.POINTER(SynthSpec), ctypes.POINTER(CommitArgs)]),
     "hq_synth_commit_lag_dev": (ctypes.c_int, [_vp, ctypes.POINTER(SynthSpec),
                                                ctypes.POINTER(LagArgs), _vp]),
@@ -1712,6 +1731,37 @@ class Worker:
             buf = (ctypes.c_char * (count * dt.itemsize)).from_address(getattr(out, name))
             res[name] = np.frombuffer(buf, dt).copy() if copy else np.frombuffer(buf, dt)
         return res
+
+    def config_changes(self, changes, copy=True):
+        """hq_worker_config_changes: `changes` is a CONFIG_CHANGE_DTYPE array or a sequence of
+        (handle, HQ_CC_* type, node_id), each group at most once. Returns a dict: 'status' (uint32,
+        HQ_CC_* per change), 'commits' (COMMIT_EVENT_DTYPE: a removal's tryCommit that advanced),
+        'n_applied', 'n_noop', 'n_fallback', 'n_suspended', 'gpu_ns'. With copy=False the arrays
+        are views of the worker's buffers, valid until its next config_changes call."""
+        if not isinstance(changes, np.ndarray):
+            changes = np.array([tuple(c) for c in changes], CONFIG_CHANGE_DTYPE)
+        changes = np.ascontiguousarray(changes, CONFIG_CHANGE_DTYPE)
+        n = len(changes)
+        out = ConfigOutput()
+        self._check(lib.hq_worker_config_changes(self.h, n, _p(changes) if n else None,
+                                                 ctypes.byref(out)), "hq_worker_config_changes")
+        res = {k: getattr(out, k) for k in ("n_applied", "n_noop", "n_fallback", "n_suspended",
+                                            "gpu_ns")}
+        for name, count, dt in (("status", n, np.dtype("<u4")),
+                                ("commits", out.n_commits, COMMIT_EVENT_DTYPE)):
+            if count == 0:
+                res[name] = np.zeros(0, dt)
+                continue
+            buf = (ctypes.c_char * (count * dt.itemsize)).from_address(getattr(out, name))
+            res[name] = np.frombuffer(buf, dt).copy() if copy else np.frombuffer(buf, dt)
+        return res
+
+    def readback_count(self) -> int:
+        """hq_worker_readback_count: how often the device-resident state was copied back."""
+        n = ctypes.c_uint64(0)
+        self._check(lib.hq_worker_readback_count(self.h, ctypes.byref(n)),
+                    "hq_worker_readback_count")
+        return n.value
 
 
 class StepJobs:

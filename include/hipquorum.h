@@ -1626,6 +1626,75 @@ typedef struct hq_heartbeat_batches {
 int hq_worker_heartbeat_batches(hq_worker *w, uint64_t n_groups, const uint32_t *groups,
                                 const hq_heartbeat_wire_config *cfg, hq_heartbeat_batches *out);
 
+/* ---------------------------------------------------------------- membership changes -------- */
+/*
+ * A membership change applied to the worker's quorum state where it lives: what
+ * node.ApplyConfigChange (node.go:229-251) -> Peer.ApplyConfigChange (peer.go:137-149) ->
+ * handleNodeConfigChange (raft.go:1540-1559) -> addNode / addObserver / addWitness / removeNode
+ * (raft.go:1136-1199) do to r.remotes / r.observers / r.witnesses, and the tryCommit removeNode
+ * ends with on a leader (raft.go:1194-1198: a smaller quorum may commit entries that were waiting).
+ * A device worker edits the resident member records with one small kernel (hq_config.hip); nothing
+ * is read back and no member's match is asked of the caller. A host worker gives the same output
+ * from its own records. Additions to ABI 21 (new symbols only); nothing of the step changes.
+ *
+ * Per change, exactly the reference's:
+ *   ADD_NODE      a remote already: NOOP; an observer: promoted to a remote with its match and
+ *                 active flag kept (raft.go:1145-1148); else a new remote, match 0, inactive
+ *   ADD_OBSERVER / ADD_WITNESS   one already: NOOP; else a new one, match 0, inactive
+ *   REMOVE_NODE   the member is deleted whatever its role (APPLIED; a non-member: NOOP); then, on a
+ *                 leader, tryCommit: the quorum-th largest voting match q commits iff
+ *                 q > committed && term_start <= q <= last_index, and the group gets a commit record
+ * Nothing else of the group changes: its pending ReadIndex queue, its votes, term, state and the
+ * other members' match / active survive (the confirmed and vote bitmaps are remapped to the new
+ * voting slots). clearPendingConfigChange, abortLeaderTransfer and broadcastReplicateMessage stay
+ * with the caller: a commit record tells it to broadcast.
+ *
+ * Member order (hq_worker_get_group, the heartbeat word's bit i, the route column): a new member
+ * is appended at position n_members; a removed member's successors move down by one; a promoted
+ * observer keeps its position. The route column moves with it (a removed member's word is
+ * deleted, the vacated last word and a new member's word are HQ_ROUTE_NONE).
+ *
+ * HQ_CC_FALLBACK — the change cannot be followed exactly; nothing is applied and the group is
+ * suspended as by a step's fallback (hq_worker_set_group resumes it): (a) it would give more than
+ * n_max voting members, or more than 16 members on a device worker (64 on a host worker); (b) it
+ * removes the worker's own node (dragonboat stops that node, node.go:241-244); (c) it removes a
+ * voting member whose slot holds a recorded vote (granted / rejected) or an acknowledgement of a
+ * pending ReadIndex: the reference keeps those entries, by node id, and goes on counting them.
+ *
+ * HQ_E_INVAL, with nothing applied to any group: a NULL argument, an unknown handle, a group
+ * listed twice, an unknown type, node_id 0, ADD_NODE of a witness (the reference panics,
+ * raft.go:1153-1154), ADD_OBSERVER / ADD_WITNESS of a member in another role.
+ */
+#define HQ_CC_ADD_NODE     0u   /* raftpb.ConfigChangeType, raft.proto:62-67 */
+#define HQ_CC_REMOVE_NODE  1u
+#define HQ_CC_ADD_OBSERVER 2u
+#define HQ_CC_ADD_WITNESS  3u
+
+#define HQ_CC_APPLIED   0u  /* the group's members changed as the reference's do */
+#define HQ_CC_NOOP      1u  /* nothing to change (already a member in that role; removing a non-member) */
+#define HQ_CC_FALLBACK  2u  /* the worker cannot follow this change exactly: nothing applied, the group is
+                               suspended from here on (hq_worker_set_group resumes it) */
+#define HQ_CC_SUSPENDED 3u  /* the group was suspended already: nothing applied */
+
+typedef struct hq_config_change { uint32_t group, type; uint64_t node_id; } hq_config_change;
+typedef struct hq_config_output {
+    const uint32_t *status;            /* [n], HQ_CC_* per change, input order */
+    const hq_commit_event *commits;    /* removeNode's tryCommit that advanced, input order */
+    uint64_t n_commits, n_applied, n_noop, n_fallback, n_suspended;
+    uint64_t gpu_ns;                   /* device workers: GPU time between the call's events, else 0 */
+} hq_config_output;
+/* Apply changes[0 .. n): `group` is a handle, each group at most once (the reference has at most
+ * one config change pending per group). Synchronous; called between steps, where the reference
+ * applies the change under raftMu. Changes queued with hq_worker_set_group / _add_group are
+ * uploaded first. The arrays are owned by the worker and valid until its next
+ * hq_worker_config_changes or close (the last hq_step_output stays valid). n = 0 is HQ_OK. */
+int hq_worker_config_changes(hq_worker *w, uint64_t n, const hq_config_change *changes,
+                             hq_config_output *out);
+/* How often the worker has copied its device-resident state back to the host mirror
+ * (hq_worker_get_group / _set_group / _add_group on a worker whose device state is newer; always 0
+ * for a host worker): what a caller watches to keep a path free of readbacks. */
+int hq_worker_readback_count(hq_worker *w, uint64_t *n);
+
 /* ---------------------------------------------------------------- synthetic inputs ---------- */
 
 /*

@@ -554,6 +554,74 @@ func (x *Worker) HeartbeatBatches(groups []uint32, n int, deploymentID uint64, s
 	return o, nil
 }
 
+// ConfigChange is one membership change of ApplyConfigChanges: Group is the worker's handle of the
+// cluster, Type the pb.ConfigChangeType (AddNode 0, RemoveNode 1, AddObserver 2, AddWitness 3).
+type ConfigChange struct {
+	Group  uint32
+	Type   pb.ConfigChangeType
+	NodeID uint64
+}
+
+// ConfigChangeOutput is the result of ApplyConfigChanges. The arrays live in the worker's buffers
+// and are valid until its next ApplyConfigChanges call; the last step's Output stays valid.
+type ConfigChangeOutput struct {
+	c C.hq_config_output
+	n int
+}
+
+// Config-change statuses (HQ_CC_*): Fallback means nothing was applied and the group is suspended
+// until SetGroup re-syncs it from the CPU raft; Suspended that it was suspended already.
+const (
+	ConfigApplied   = uint32(C.HQ_CC_APPLIED)
+	ConfigNoop      = uint32(C.HQ_CC_NOOP)
+	ConfigFallback  = uint32(C.HQ_CC_FALLBACK)
+	ConfigSuspended = uint32(C.HQ_CC_SUSPENDED)
+)
+
+// ApplyConfigChanges applies membership changes to the worker's quorum state
+// (hq_worker_config_changes: handleNodeConfigChange, raft.go:1540-1559, with removeNode's
+// tryCommit, raft.go:1194-1198), each group at most once. It is called between steps, where
+// node.ApplyConfigChange holds raftMu (node.go:229-251). A device worker edits its resident member
+// records with one small kernel: nothing of the state is read back.
+func (x *Worker) ApplyConfigChanges(changes []ConfigChange) (*ConfigChangeOutput, error) {
+	o := &ConfigChangeOutput{n: len(changes)}
+	cs := make([]C.hq_config_change, len(changes))
+	for i, ch := range changes {
+		cs[i] = C.hq_config_change{group: C.uint32_t(ch.Group), _type: C.uint32_t(ch.Type),
+			node_id: C.uint64_t(ch.NodeID)}
+	}
+	var cp *C.hq_config_change
+	if len(cs) > 0 {
+		cp = &cs[0]
+	}
+	if rc := C.hq_worker_config_changes(x.w, C.uint64_t(len(cs)), cp, &o.c); rc != C.HQ_OK {
+		return nil, x.err(rc)
+	}
+	return o, nil
+}
+
+// Status lists one status per change, in input order.
+func (o *ConfigChangeOutput) Status() []uint32 {
+	if o.n == 0 {
+		return nil
+	}
+	return unsafe.Slice((*uint32)(unsafe.Pointer(o.c.status)), o.n)
+}
+
+// Commits lists the groups whose committed index a removal advanced (the caller then broadcasts
+// Replicate for them, raft.go:1195-1197), in input order.
+func (o *ConfigChangeOutput) Commits() []C.hq_commit_event {
+	if o.c.n_commits == 0 {
+		return nil
+	}
+	return unsafe.Slice((*C.hq_commit_event)(unsafe.Pointer(o.c.commits)), int(o.c.n_commits))
+}
+
+// Fallbacks is the number of groups the call suspended, GPUNanos the HIP-event time of the call
+// (0 on a host worker).
+func (o *ConfigChangeOutput) Fallbacks() uint64 { return uint64(o.c.n_fallback) }
+func (o *ConfigChangeOutput) GPUNanos() uint64  { return uint64(o.c.gpu_ns) }
+
 // StateChanges lists the step's leader / follower / candidate transitions.
 func (o *Output) StateChanges() []C.hq_state_change {
 	if o.c.n_state_changes == 0 {
