@@ -234,7 +234,8 @@ __device__ bool decode_event(ByteReader &r, DPrev &pv, hq_event &v) {
             pv.last &= 7u;
             if (h0 & 0x80) {       // the consecutive form: the first sender, the rest follow
                 uint64_t f0;
-                if (!dvar(r, f0) || f0 + m > 0xFFFFFFFFull) return false;
+                // (m <= 0xFFFF above; compared without the sum, which wraps for f0 near 2^64)
+                if (!dvar(r, f0) || f0 > 0xFFFFFFFFull - m) return false;
                 pv.run_from = (uint32_t)f0;
                 pv.last |= 8u;
             }

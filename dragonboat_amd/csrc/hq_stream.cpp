@@ -103,7 +103,8 @@ inline bool repeats(const Ev &e, const Prev &pv) {
 template <class From>
 inline uint8_t *put_run(uint8_t *p, uint32_t m, From from) {
     const uint64_t f0 = from(0);
-    bool seq = f0 + m <= 0xFFFFFFFFull;
+    // s0 + m <= 2^32 - 1, compared without the sum: s0 near 2^64 must not wrap into the form
+    bool seq = f0 <= 0xFFFFFFFFull - m;
     for (uint32_t j = 1; j < m && seq; ++j) seq = from(j) == f0 + j;
     if (seq) {
         *p++ = (uint8_t)(HQ_EV_MESSAGE | kCodeRun << 3 | 0x80);
@@ -557,7 +558,10 @@ bool decode_one(const uint8_t *&p, const uint8_t *end, Prev &pv, uint64_t &run_l
             pv.run_seq = (h & 0x80) != 0;
             if (pv.run_seq) {          // the consecutive form: the first sender, the rest follow
                 uint64_t f0;
-                if (!get(p, end, f0) || f0 + run_left > 0xFFFFFFFFull) return false;
+                // (the encoder's bound, without the sum: neither operand may wrap it)
+                if (!get(p, end, f0) || run_left > 0xFFFFFFFFull ||
+                    f0 > 0xFFFFFFFFull - run_left)
+                    return false;
                 pv.run_from = (uint32_t)f0;
             }
         }

@@ -1120,7 +1120,11 @@ int hq_worker_set_wait(hq_worker *w, uint32_t mode, uint32_t poll_us, uint32_t s
  *                     log_index / ctx — with other senders; a varint m >= 1, then m sender
  *                     varints (bit 6 of a run's header is 0; bit 7 0). Bit 7 set (ABI 21): the
  *                     consecutive form, senders s0, s0 + 1, .., s0 + m - 1 — a varint m, then s0
- *                     alone (s0 + m < 2^32). The acks of a steady leader's followers come as
+ *                     alone. The form holds 32-bit senders only: s0 + m <= 2^32 - 1 as integers,
+ *                     i.e. s0 <= 2^32 - 1 - m (compared so, never through a 64-bit sum: a run
+ *                     ending at node id 2^64 - 1 would wrap it). The encoders list the senders
+ *                     of any other run; a decoder takes a header outside the bound as an event
+ *                     that does not decode. The acks of a steady leader's followers come as
  *                     runs: 2 + m bytes for m one-byte senders instead of 2 m, 3 bytes when the
  *                     followers' node ids are consecutive.
  *                     The encoders write a run for 3 to 6 such events (6: a run with 10-byte
