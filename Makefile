@@ -9,6 +9,7 @@ OBJS := $(LIBDIR)/hq_runtime.o $(LIBDIR)/hq_commit.o $(LIBDIR)/hq_commit_tiles.o
         $(LIBDIR)/hq_commit_lag.o $(LIBDIR)/hq_bits.o $(LIBDIR)/hq_ri_multi.o $(LIBDIR)/hq_synth.o \
         $(LIBDIR)/hq_ingest.o $(LIBDIR)/hq_table.o $(LIBDIR)/hq_pack.o $(LIBDIR)/hq_worker.o \
         $(LIBDIR)/hq_wire.o $(LIBDIR)/hq_stream.o $(LIBDIR)/hq_jobs.o $(LIBDIR)/hq_dstep.o \
+        $(LIBDIR)/hq_dstep_step.o $(LIBDIR)/hq_dstep_layout.o $(LIBDIR)/hq_dstep_run.o \
         $(LIBDIR)/hq_engine.o $(LIBDIR)/hq_wire_frame.o $(LIBDIR)/hq_wire_dev.o \
         $(LIBDIR)/hq_heartbeat.o $(LIBDIR)/hq_heartbeat_wire.o $(LIBDIR)/hq_wire_frame_dev.o \
         $(LIBDIR)/hq_config.o
@@ -16,6 +17,7 @@ SRCS := $(CSRC)/hq_runtime.hip $(CSRC)/hq_commit.hip $(CSRC)/hq_commit_tiles.hip
         $(CSRC)/hq_commit_lag.hip $(CSRC)/hq_bits.hip $(CSRC)/hq_ri_multi.hip $(CSRC)/hq_synth.hip \
         $(CSRC)/hq_ingest.hip $(CSRC)/hq_table.hip $(CSRC)/hq_pack.cpp $(CSRC)/hq_worker.cpp \
         $(CSRC)/hq_wire.cpp $(CSRC)/hq_stream.cpp $(CSRC)/hq_jobs.cpp $(CSRC)/hq_dstep.hip \
+        $(CSRC)/hq_dstep_step.hip $(CSRC)/hq_dstep_layout.hip $(CSRC)/hq_dstep_run.hip \
         $(CSRC)/hq_engine.hip $(CSRC)/hq_wire_frame.cpp $(CSRC)/hq_wire_dev.hip \
         $(CSRC)/hq_heartbeat.hip $(CSRC)/hq_heartbeat_wire.hip $(CSRC)/hq_wire_frame_dev.hip \
         $(CSRC)/hq_config.hip
@@ -46,12 +48,10 @@ oracle:
 
 # tuning variants (one library each, for A/B runs via HQ_LIB_PATH, tools/ab_libs.sh):
 #   lib_ivN    records per lane of the table ingest kernels
-#   lib_swN    the device step engine's kernels asked for N waves per SIMD
 #   lib_ingnostore / lib_ingnoload the grouped table ingest without its table stores / loads (timing probes: wrong output)
 #   lib_encspawn the threaded event encoder spawning its threads per call (before the task pool)
 #   lib_encprof the threaded encoder's per-range start / barrier arrival per call (stderr)
 #   lib_engprof the engine's per-workgroup clocks and tile counts (hq_engine_wgprof; tools/engine_wgprof.py)
-#   lib_notakerun the device step taking every run member one event at a time (no take_run; A/B)
 define variant
 	@mkdir -p $(dir $@)
 	$(HIPCC) $(HIPFLAGS) $(1) -shared -o $@ $(SRCS)
@@ -73,10 +73,6 @@ tools/lib_encprof/libhipquorum.so: $(SRCS) $(DEPS)
 	$(call variant,-DHQ_ENC_PROF)
 tools/lib_engprof/libhipquorum.so: $(SRCS) $(DEPS)
 	$(call variant,-DHQ_ENGINE_WGPROF)
-tools/lib_notakerun/libhipquorum.so: $(SRCS) $(DEPS)
-	$(call variant,-DHQ_NO_TAKE_RUN)
-tools/lib_sw%/libhipquorum.so: $(SRCS) $(DEPS)
-	$(call variant,-DHQ_STEP_WAVES=$*)
 # binned-ingest A/B (tools/ab_bin.sh): kernel parts removed (HQ_BIN_AB) or smaller regions
 tools/lib_binab%/libhipquorum.so: $(SRCS) $(DEPS)
 	$(call variant,-DHQ_BIN_AB=$*)
@@ -86,8 +82,6 @@ tools/lib_bintpb%/libhipquorum.so: $(SRCS) $(DEPS)
 tools/binprof: tools/binprof.hip $(SRCS) $(DEPS) $(OBJS)
 	$(HIPCC) $(HIPFLAGS) -c -o tools/binprof.o tools/binprof.hip
 	$(HIPCC) $(HIPFLAGS) -pthread -o $@ tools/binprof.o $(filter-out $(LIBDIR)/hq_table.o,$(OBJS))
-tools/lib_stepchunks%/libhipquorum.so: $(SRCS) $(DEPS)
-	$(call variant,-DHQ_STEP_CHUNKS=$*)
 # persistent-engine experiments (tools/ab_engine.py): multi-batch loop / flat / claim kernels beside
 # the engine, in a library of their own linked against the product library
 tools/lib_engexp/libengexp.so: tools/engine_exp.hip $(LIB) $(DEPS)

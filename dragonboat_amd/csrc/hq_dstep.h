@@ -1,6 +1,6 @@
 // hq_dstep.h — the device step engine of the step worker (hq_worker_open_ex with
 // HQ_WORKER_ON_DEVICE), shared between hq_worker.cpp (plain C++, the host side: state mirror,
-// validation, outputs) and hq_dstep.hip (the kernels). Internal to libhipquorum.so.
+// validation, outputs) and the engine's files (hq_dstep.hip, _step, _layout, _run). Internal.
 #pragma once
 
 #include <cstdint>

@@ -5,7 +5,7 @@
 // instead of the 56-byte row, so that a host-fed step crosses PCIe ~10x faster. Host code: the
 // encoder a producer holding rows can call (the wire decoder and a caller's own producer can
 // write the stream directly) and the decoder the host worker uses for stream input; the device
-// twin of the decoder is in hq_dstep.hip.
+// twin of the decoder is in hq_dstep_step.hip.
 #include <algorithm>
 #include <atomic>
 #include <chrono>

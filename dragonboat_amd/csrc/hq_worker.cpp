@@ -97,7 +97,7 @@ struct hq_worker {
     hq_ctx *ctx = nullptr;
     int device = -1;
     uint32_t n_max = 0;
-    // HQ_WORKER_ON_DEVICE: the group state lives on the GPU (hq_dstep.hip) and a step is one
+    // HQ_WORKER_ON_DEVICE: the group state lives on the GPU (hq_dstep*.hip) and a step is one
     // launch pair; the host records below are a mirror, refreshed from the device on demand
     hq_dstep *dstep = nullptr;
     bool host_stale = false;              // the device holds newer state than the mirror
@@ -924,7 +924,7 @@ int hq_worker::device_step_done(int rc, const hq_dstep_in &inp, hq_step_output *
                                 uint64_t t1) {
     if (rc == HQ_E_INVAL && dout.input_error) {
         const uint32_t e = dout.input_error;
-        if (e & (16 | 32))        // (hq_dstep.hip kErrScan / kErrTicket: not the input's fault)
+        if (e & (16 | 32))        // (hq_dstep_k.h kErrScan / kErrTicket: not the input's fault)
             return fail(HQ_E_STATE, "hq_worker_step: the device step's scan of the ReadyToRead "
                                     "places or its launch order failed (internal); no group "
                                     "state was written");
@@ -1811,8 +1811,6 @@ int hq_worker_step_device_rows(hq_worker *w, uint64_t n, const uint32_t *groups,
 // for any other set of jobs; else the first job's failure (each job's in its rc).
 int hq_worker_step_jobs_fused(hq_step_job *jobs, uint32_t count) {
     if (count < 2 || count > kDStepMaxJobs) return kJobsNotFused;
-    if (const char *v = std::getenv("HQ_STEP_JOBS_FUSED"))
-        if (std::atoi(v) == 0) return kJobsNotFused;
     int device = -1;
     for (uint32_t j = 0; j < count; ++j) {
         const hq_step_job &b = jobs[j];

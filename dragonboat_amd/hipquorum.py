@@ -1487,7 +1487,7 @@ class Worker:
                  commit_column: bool = False, commit_advance: bool = False,
                  ready_compact: bool = False, ready_slots: bool = False):
         """on_device: HQ_WORKER_ON_DEVICE, the group state resident on the GPU and every event
-        taken there (hq_dstep.hip); otherwise the host worker (events on the host, decisions
+        taken there (hq_dstep_step.hip); otherwise the host worker (events on the host, decisions
         in GPU passes). commit_column: HQ_WORKER_COMMIT_COLUMN (results carry
         'committed_column' instead of 'commits' when most listed groups commit);
         commit_advance: HQ_WORKER_COMMIT_ADVANCE ('committed_advance', u32 per listed group,

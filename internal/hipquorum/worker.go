@@ -50,7 +50,7 @@ func OpenWorker(device, nMax int) (*Worker, error) {
 
 // OpenDeviceWorker opens a worker whose groups' quorum state is resident in HBM: one GPU thread
 // per group takes its events in order, every decision at the event that triggers it
-// (hq_dstep.hip); commits come back as 4-byte advances when a quarter of the listed groups
+// (hq_dstep_step.hip); commits come back as 4-byte advances when a quarter of the listed groups
 // commit, else as one word per listed group or as records; ReadyToReads as 24-byte records
 // (EachReady).
 func OpenDeviceWorker(device, nMax int) (*Worker, error) {

@@ -1,4 +1,4 @@
-"""Round 6 forms of the device step (hq_dstep.hip) against the forms they replace, bit for bit:
+"""Round 6 forms of the device step (hq_dstep_step.hip) against the forms they replace, bit for bit:
 
 * HQ_WORKER_READY_SLOTS — the single ReadyToReads written by pass A into per-tile slots (the
   reference's consumer is node.processReadyToRead, node.go:1026-1031): merged with the list by

@@ -16,7 +16,7 @@ CASES = list(sc.all_cases())
 
 
 MODES = [False, True]
-MODE_IDS = ["host", "device"]      # the host worker / HQ_WORKER_ON_DEVICE (hq_dstep.hip)
+MODE_IDS = ["host", "device"]      # the host worker / HQ_WORKER_ON_DEVICE (hq_dstep*.hip)
 # (on_device, stream): events as rows or as an event stream (hq_worker_step_stream)
 FEEDS = [(False, False), (True, False), (True, True), (False, True), (True, "sized"),
          (False, "sized"), (True, "sized-column"), (True, "sized-advance"), (True, "sized16"),
@@ -566,7 +566,7 @@ def test_pinned_sized_stream_equals_pageable(hq, flags):
                               "stream-advance"])
 def test_chunked_device_step_equals_host_worker(hq, stream):
     """A step of >= 256 Ki groups runs in 4 chunks whose copies overlap the neighbouring chunks'
-    passes (hq_dstep.hip); its lists equal the host worker's on the same events (the host
+    passes (hq_dstep_run.hip); its lists equal the host worker's on the same events (the host
     worker is checked against the oracle above), in the same order. With the advance column a
     stream's pass A also writes the single ReadyToReads at their places (ready_tail's chained
     scan across the chunks' launches: byte chunks for a sized stream, group chunks for one with
@@ -889,7 +889,7 @@ def test_ready_compact_needs_the_device_worker(hq):
 @pytest.mark.parametrize("seed", [31, 32])
 def test_consecutive_runs_device_equals_reference(hq, seed, stream):
     """Runs of acks from consecutive node ids, which the device takes a run at a time where each
-    member can only raise its match and mark itself active (hq_dstep.hip take_run), against the
+    member can only raise its match and mark itself active (hq_dstep_step.hip take_run), against the
     reference replay (oracle/qref_step.c) taking the same events one at a time: every output list
     and every group's state equal, no fallback."""
     rng = np.random.default_rng(seed)
