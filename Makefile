@@ -12,7 +12,7 @@ OBJS := $(LIBDIR)/hq_runtime.o $(LIBDIR)/hq_commit.o $(LIBDIR)/hq_commit_tiles.o
         $(LIBDIR)/hq_dstep_step.o $(LIBDIR)/hq_dstep_layout.o $(LIBDIR)/hq_dstep_run.o \
         $(LIBDIR)/hq_engine.o $(LIBDIR)/hq_wire_frame.o $(LIBDIR)/hq_wire_dev.o \
         $(LIBDIR)/hq_heartbeat.o $(LIBDIR)/hq_heartbeat_wire.o $(LIBDIR)/hq_wire_frame_dev.o \
-        $(LIBDIR)/hq_config.o
+        $(LIBDIR)/hq_config.o $(LIBDIR)/hq_groups.o
 SRCS := $(CSRC)/hq_runtime.hip $(CSRC)/hq_commit.hip $(CSRC)/hq_commit_tiles.hip \
         $(CSRC)/hq_commit_lag.hip $(CSRC)/hq_bits.hip $(CSRC)/hq_ri_multi.hip $(CSRC)/hq_synth.hip \
         $(CSRC)/hq_ingest.hip $(CSRC)/hq_table.hip $(CSRC)/hq_pack.cpp $(CSRC)/hq_worker.cpp \
@@ -20,7 +20,7 @@ SRCS := $(CSRC)/hq_runtime.hip $(CSRC)/hq_commit.hip $(CSRC)/hq_commit_tiles.hip
         $(CSRC)/hq_dstep_step.hip $(CSRC)/hq_dstep_layout.hip $(CSRC)/hq_dstep_run.hip \
         $(CSRC)/hq_engine.hip $(CSRC)/hq_wire_frame.cpp $(CSRC)/hq_wire_dev.hip \
         $(CSRC)/hq_heartbeat.hip $(CSRC)/hq_heartbeat_wire.hip $(CSRC)/hq_wire_frame_dev.hip \
-        $(CSRC)/hq_config.hip
+        $(CSRC)/hq_config.hip $(CSRC)/hq_groups.hip
 DEPS := $(wildcard $(CSRC)/*.h) include/hipquorum.h
 CXX ?= g++
 CXXFLAGS ?= -O3 -std=c++17 -fPIC -pthread -Wall -Wextra

@@ -28,6 +28,7 @@
 #include "../../include/hipquorum.h"
 #include "hq_config.h"
 #include "hq_dstep.h"
+#include "hq_groups.h"
 #include "hq_heartbeat.h"
 #include "hq_heartbeat_wire.h"
 
@@ -85,6 +86,10 @@ uint64_t now_ns() {
         .count();
 }
 
+hq_dmember to_device_member(const Member &m) {    // a pool record as the device keeps it
+    return hq_dmember{m.node_id, m.match, m.role, m.active, m.order, {0, 0, 0, 0, 0}};
+}
+
 bool is_response_type(uint32_t t) {       // isResponseMessageType (internal/raft/utils.go)
     return t == HQ_MSG_REPLICATE_RESP || t == HQ_MSG_REQUEST_VOTE_RESP ||
            t == HQ_MSG_HEARTBEAT_RESP || t == 20 /* ReadIndexResp */ ||
@@ -125,6 +130,14 @@ struct hq_worker {
     std::vector<uint32_t> cc_status;
     std::vector<hq_commit_event> cc_commits;
     uint64_t readbacks = 0;               // sync_from_device calls that copied the state back
+    // hq_worker_get_groups / _set_groups: a device worker's buffers (first call) and the last
+    // get_groups' output
+    hq_groups_dev *grp = nullptr;
+    std::vector<hq_worker_group> gg_groups;
+    std::vector<hq_member> gg_members;
+    std::vector<hq_read_status> gg_reads;
+    std::vector<uint64_t> gg_moff, gg_roff;
+    std::vector<uint16_t> gg_granted, gg_rejected, gg_rconf;
     std::vector<hq_event> decoded;        // host worker: a stream step's rows
     std::vector<uint64_t> sized_off, sized_boff;   // host worker: a sized stream's prefixes
     std::vector<uint32_t> sized_groups;            // and its implicit handles
@@ -191,7 +204,11 @@ struct hq_worker {
     int step_on_device(const hq_dstep_in &in, hq_step_output *out);
     int device_step_done(int rc, const hq_dstep_in &in, hq_step_output *out, uint64_t t0,
                          uint64_t t1);
+    int check_group(const hq_worker_group *src, const hq_member *m, int *self, int *n_voting);
     int load_group(Group &g, const hq_worker_group *src, const hq_member *m, bool fresh);
+    bool emit_group(const hq_dgroup &d, const hq_dread *r, const hq_dmember *m);
+    int get_groups(uint64_t n, const uint32_t *handles, hq_groups_output *out);
+    int set_groups(uint64_t n, const hq_worker_group *gs, const hq_member *ms, uint64_t *gpu_ns);
     int step(const hq_step_input *in, hq_step_output *out);
     int heartbeats(uint64_t n, const uint32_t *list, hq_heartbeat_output *out);
     int heartbeat_batches(uint64_t n, const uint32_t *list, const hq_heartbeat_wire_config *cfg,
@@ -214,9 +231,9 @@ struct hq_worker {
 };
 
 // ------------------------------------------------------------------------------ state ------
-// Validates and loads a group; `fresh` groups get a new member range, others reuse theirs when
-// it is large enough.
-int hq_worker::load_group(Group &g, const hq_worker_group *src, const hq_member *m, bool fresh) {
+// What a group must satisfy to be loaded (nothing is changed); the node's place in the list and
+// the voting members' count on the way.
+int hq_worker::check_group(const hq_worker_group *src, const hq_member *m, int *self_out, int *n_voting_out) {
     const uint32_t n = src->n_members;
     if (n < 1 || !m) return fail(HQ_E_INVAL, "group has no members");
     if (n > 64) return fail(HQ_E_INVAL, "more than 64 members");
@@ -233,6 +250,17 @@ int hq_worker::load_group(Group &g, const hq_worker_group *src, const hq_member 
     if (n_voting > (int)n_max) return fail(HQ_E_INVAL, "more voting members than n_max");
     if (dstep && n > kDMembers)
         return fail(HQ_E_INVAL, "more than 16 members on the device path (HQ_WORKER_ON_DEVICE)");
+    *self_out = self;
+    *n_voting_out = n_voting;
+    return HQ_OK;
+}
+
+// Validates and loads a group; `fresh` groups get a new member range, others reuse theirs when
+// it is large enough.
+int hq_worker::load_group(Group &g, const hq_worker_group *src, const hq_member *m, bool fresh) {
+    int self = -1, n_voting = 0;
+    if (int rc = check_group(src, m, &self, &n_voting)) return rc;
+    const uint32_t n = src->n_members;
     if (fresh || g.mem_cap < n) {
         g.mem = (uint32_t)pool.size();
         g.mem_cap = (uint8_t)n;
@@ -829,10 +857,7 @@ int hq_worker::sync_to_device() {
         for (uint64_t i = 0; i < ng; ++i)
             to_device_record(groups[dev_groups + i], dg[i], dr.data() + i * kDReads);
         std::vector<hq_dmember> dm(nm);
-        for (uint64_t i = 0; i < nm; ++i) {
-            const Member &m = pool[dev_members + i];
-            dm[i] = hq_dmember{m.node_id, m.match, m.role, m.active, m.order, {0, 0, 0, 0, 0}};
-        }
+        for (uint64_t i = 0; i < nm; ++i) dm[i] = to_device_member(pool[dev_members + i]);
         int rc = hq(hq_dstep_put(dstep, dev_groups, ng, dg.data(), dr.data(), dev_members, nm,
                                  dm.data()), "hq_dstep_put");
         if (rc) return rc;
@@ -845,10 +870,7 @@ int hq_worker::sync_to_device() {
         hq_dread dr[kDReads];
         to_device_record(g, dg, dr);
         std::vector<hq_dmember> dm(g.n_members);
-        for (uint32_t i = 0; i < g.n_members; ++i) {
-            const Member &m = pool[g.mem + i];
-            dm[i] = hq_dmember{m.node_id, m.match, m.role, m.active, m.order, {0, 0, 0, 0, 0}};
-        }
+        for (uint32_t i = 0; i < g.n_members; ++i) dm[i] = to_device_member(pool[g.mem + i]);
         int rc = hq(hq_dstep_put(dstep, h, 1, &dg, dr, g.mem, g.n_members, dm.data()),
                     "hq_dstep_put");
         if (rc) return rc;
@@ -1458,8 +1480,204 @@ int hq_worker::config_changes(uint64_t n, const hq_config_change *ch, hq_config_
     return HQ_OK;
 }
 
+// ------------------------------------------------------------------------------ listed groups --
+// hq_worker_get_groups / hq_worker_set_groups (include/hipquorum.h "listed groups"): a device
+// worker moves one packed record per listed group between the resident state and pinned host
+// memory (hq_groups.hip); a host worker packs the same records from its own. Neither call reads
+// the device state back or touches host_stale.
+
+// One group of a get_groups output from its device-form records (members in pool order): the
+// group as get_group fills it, members in the caller's order, masks in the caller's terms.
+bool hq_worker::emit_group(const hq_dgroup &d, const hq_dread *r, const hq_dmember *m) {
+    gg_groups.push_back(hq_worker_group{d.cluster_id, d.node_id, d.term, d.committed, d.last, d.term_start,
+                                        d.state, d.n_members, d.n_reads,
+                                        (d.flags & kDSuspended) ? 1u : 0u});
+    const size_t m0 = gg_members.size();
+    gg_members.resize(m0 + d.n_members);
+    for (uint32_t i = 0; i < d.n_members; ++i) {
+        if (m[i].order >= d.n_members) return false;
+        gg_members[m0 + m[i].order] = hq_member{m[i].node_id, m[i].match, m[i].role, m[i].active};
+    }
+    gg_moff.push_back(gg_members.size());
+    for (uint32_t k = 0; k < d.n_reads; ++k) {
+        uint32_t c = 0;
+        for (uint32_t s = 0; s < HQ_MAX_VOTERS; ++s) c += (r[k].confirmed >> s) & 1u;
+        gg_reads.push_back(hq_read_status{r[k].index, r[k].from, r[k].low, r[k].high, c, 0});
+        gg_rconf.push_back(grp_slots_to_list(r[k].confirmed, d.n_voting, m));
+    }
+    gg_roff.push_back(gg_reads.size());
+    gg_granted.push_back(grp_slots_to_list(d.granted, d.n_voting, m));
+    gg_rejected.push_back(grp_slots_to_list(d.rejected, d.n_voting, m));
+    return true;
+}
+
+int hq_worker::get_groups(uint64_t n, const uint32_t *handles, hq_groups_output *out) {
+    // every check the host can make first: nothing is queued for a refused list
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint64_t h = handles ? handles[i] : i;
+        if (h >= groups.size()) return fail(HQ_E_INVAL, "hq_worker_get_groups: unknown group handle");
+        if (groups[h].n_members > kDMembers)
+            return fail(HQ_E_INVAL, "hq_worker_get_groups: a group of more than 16 members");
+    }
+    for (auto *v : {&gg_granted, &gg_rejected, &gg_rconf}) v->clear();
+    gg_groups.clear();
+    gg_members.clear();
+    gg_reads.clear();
+    gg_moff.assign(1, 0);
+    gg_roff.assign(1, 0);
+    gg_groups.reserve(n);
+    gg_moff.reserve(n + 1);
+    gg_roff.reserve(n + 1);
+    gg_granted.reserve(n);
+    gg_rejected.reserve(n);
+    uint64_t gpu_ns = 0;
+    hq_dgroup dg;
+    hq_dread dr[kDReads];
+    hq_dmember dm[kDMembers];
+    if (dstep) {
+        int rc = sync_to_device();                  // pending add / set_group first, as a step does
+        if (rc) return rc;
+        if (!grp && (rc = hq(hq_groups_dev_open(ctx, &grp), "hq_worker_get_groups"))) return rc;
+        hq_grp_record *recs = nullptr;
+        uint32_t *hh = nullptr;
+        if ((rc = hq(hq_groups_dev_stage(grp, n, &recs, &hh), "hq_worker_get_groups"))) return rc;
+        if (handles) std::copy(handles, handles + n, hh);
+        hq_dstate_view st;
+        hq_dstep_view(dstep, &st);
+        uint32_t e = 0;
+        rc = hq_groups_dev_gather(grp, &st, dev_members, n, !handles, &gpu_ns, &e);
+        if (rc == HQ_E_INVAL && e)
+            return fail(HQ_E_STATE, "hq_worker_get_groups: a resident group record does not fit the "
+                                    "state's sizes (internal)");
+        if ((rc = hq(rc, "hq_worker_get_groups"))) return rc;
+        for (uint64_t i = 0; i < n; ++i) {
+            // the mirror's structure is the host's own even while its values are stale
+            const Group &g = groups[handles ? handles[i] : i];
+            bool same = grp_unpack(recs[i], dg, dr, dm) && dg.cluster_id == g.cluster_id &&
+                        dg.n_members == g.n_members && dg.n_voting == g.n_voting && dg.mem == g.mem;
+            for (uint32_t j = 0; same && j < g.n_members; ++j) same = dm[j].node_id == pool[g.mem + j].node_id;
+            if (!same || !emit_group(dg, dr, dm))
+                return fail(HQ_E_STATE, "hq_worker_get_groups: a resident group record does not match "
+                                        "the host's (internal)");
+        }
+    } else {
+        for (uint64_t i = 0; i < n; ++i) {
+            const Group &g = groups[handles ? handles[i] : i];
+            to_device_record(g, dg, dr);
+            for (uint32_t j = 0; j < g.n_members; ++j) dm[j] = to_device_member(pool[g.mem + j]);
+            if (!emit_group(dg, dr, dm)) return fail(HQ_E_STATE, "hq_worker_get_groups: member order (internal)");
+        }
+    }
+    out->groups = gg_groups.data();
+    out->members = gg_members.data();
+    out->member_offsets = gg_moff.data();
+    out->reads = gg_reads.data();
+    out->read_offsets = gg_roff.data();
+    out->granted = gg_granted.data();
+    out->rejected = gg_rejected.data();
+    out->read_confirmed = gg_rconf.data();
+    out->n_groups = n;
+    out->gpu_ns = gpu_ns;
+    return HQ_OK;
+}
+
+int hq_worker::set_groups(uint64_t n, const hq_worker_group *gs, const hq_member *ms, uint64_t *gpu_ns) {
+    // every group is checked before any is changed
+    int rc = HQ_OK;
+    uint64_t marked = 0, off = 0, extra = 0;
+    uint32_t most = 0;
+    for (; marked < n && !rc; ++marked) {
+        const hq_worker_group &g = gs[marked];
+        auto it = index.find(g.cluster_id);
+        int self = 0, nv = 0;
+        if (it == index.end()) rc = fail(HQ_E_INVAL, "hq_worker_set_groups: unknown cluster");
+        else if (groups[it->second].has(kTouched)) rc = fail(HQ_E_INVAL, "hq_worker_set_groups: a cluster is listed twice");
+        else rc = check_group(&g, ms + off, &self, &nv);
+        if (rc) break;
+        Group &cur = groups[it->second];
+        cur.set(kTouched);
+        if (cur.mem_cap < g.n_members) extra += g.n_members;   // it moves to the pool's end
+        most = std::max<uint32_t>(most, g.n_members);
+        off += g.n_members;
+    }
+    for (uint64_t i = 0; i < marked; ++i) groups[index.find(gs[i].cluster_id)->second].clear(kTouched);
+    if (rc) return rc;
+    if (pool.size() + extra > UINT32_MAX) return fail(HQ_E_NOMEM, "hq_worker_set_groups: member pool full");
+
+    hq_grp_record *recs = nullptr;
+    uint32_t *hh = nullptr;
+    if (dstep) {
+        rc = sync_to_device();                      // pending add / set_group first, as a step does
+        if (rc) return rc;
+        if (!grp && (rc = hq(hq_groups_dev_open(ctx, &grp), "hq_worker_set_groups"))) return rc;
+        if ((rc = hq(hq_groups_dev_stage(grp, n, &recs, &hh), "hq_worker_set_groups"))) return rc;
+        // the device pool stays index-identical with the host's: the ranges of the groups that move
+        // exist there before the kernel writes them and are never uploaded from the mirror
+        rc = hq(hq_dstep_reserve_members(dstep, dev_members, pool.size() + extra), "hq_worker_set_groups");
+        if (rc) return rc;
+    }
+    // load_group sets every field to_device_record reads: a stale mirror does not matter
+    off = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint32_t h = index.find(gs[i].cluster_id)->second;
+        Group g = groups[h];
+        if ((rc = load_group(g, gs + i, ms + off, false))) return rc;   // (checked above: cannot fail)
+        groups[h] = g;
+        off += gs[i].n_members;
+        if (!dstep) continue;
+        hq_dgroup dg;
+        hq_dread dr[kDReads];
+        hq_dmember dm[kDMembers];
+        to_device_record(g, dg, dr);
+        for (uint32_t j = 0; j < g.n_members; ++j) dm[j] = to_device_member(pool[g.mem + j]);
+        grp_pack(recs[i], dg, dr, dm);
+        hh[i] = h;
+    }
+    if (!dstep) return HQ_OK;
+    dev_members = pool.size();
+    hq_dstep_raise_max_members(dstep, most);        // the step's 8-slot kernels must not see 9 members
+    hq_dstate_mut st;
+    hq_dstep_view_mut(dstep, &st);
+    uint32_t e = 0;
+    uint64_t ns = 0;
+    rc = hq_groups_dev_scatter(grp, &st, dev_members, n, &ns, &e);
+    if (rc == HQ_E_INVAL && e)
+        return fail(HQ_E_STATE, "hq_worker_set_groups: a packed group record does not fit the state's "
+                                "sizes (internal)");
+    if ((rc = hq(rc, "hq_worker_set_groups"))) return rc;
+    if (gpu_ns) *gpu_ns = ns;
+    return HQ_OK;
+}
+
 // ------------------------------------------------------------------------------ C-ABI ------
 extern "C" {
+
+int hq_worker_get_groups(hq_worker *w, uint64_t n, const uint32_t *handles, hq_groups_output *out) {
+    if (!w) return HQ_E_INVAL;
+    try {
+        if (!out) return w->fail(HQ_E_INVAL, "hq_worker_get_groups: NULL argument");
+        std::memset(out, 0, sizeof *out);
+        if (n > UINT32_MAX) return w->fail(HQ_E_INVAL, "hq_worker_get_groups: too many groups listed");
+        if (n == 0) return HQ_OK;
+        return w->get_groups(n, handles, out);
+    } catch (const std::bad_alloc &) {
+        return w->fail(HQ_E_NOMEM, "hq_worker_get_groups: out of memory");
+    }
+}
+
+int hq_worker_set_groups(hq_worker *w, uint64_t n, const hq_worker_group *groups,
+                         const hq_member *members, uint64_t *gpu_ns) {
+    if (!w) return HQ_E_INVAL;
+    try {
+        if (gpu_ns) *gpu_ns = 0;
+        if (n && (!groups || !members)) return w->fail(HQ_E_INVAL, "hq_worker_set_groups: NULL argument");
+        if (n > UINT32_MAX) return w->fail(HQ_E_INVAL, "hq_worker_set_groups: a cluster is listed twice");
+        if (n == 0) return HQ_OK;
+        return w->set_groups(n, groups, members, gpu_ns);
+    } catch (const std::bad_alloc &) {
+        return w->fail(HQ_E_NOMEM, "hq_worker_set_groups: out of memory");
+    }
+}
 
 int hq_worker_config_changes(hq_worker *w, uint64_t n, const hq_config_change *changes,
                              hq_config_output *out) {
@@ -1633,6 +1851,7 @@ void hq_worker_close(hq_worker *w) {
     if (w->hb) hq_hb_dev_close(w->hb);
     if (w->hbw) hq_hbw_dev_close(w->hbw);
     if (w->cfg) hq_cfg_dev_close(w->cfg);
+    if (w->grp) hq_groups_dev_close(w->grp);
     if (w->dstep) hq_dstep_close(w->dstep);
     if (w->ctx) {
         hq_sync(w->ctx);

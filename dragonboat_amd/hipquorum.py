@@ -257,6 +257,16 @@ class ConfigOutput(ctypes.Structure):
                 ("gpu_ns", ctypes.c_uint64)]
 
 
+# listed groups (hq_worker_get_groups / hq_worker_set_groups)
+class GroupsOutput(ctypes.Structure):
+    """Mirror of ``hq_groups_output``."""
+
+    _fields_ = [("groups", _vp), ("members", _vp), ("member_offsets", _vp), ("reads", _vp),
+                ("read_offsets", _vp), ("granted", _vp), ("rejected", _vp),
+                ("read_confirmed", _vp), ("n_groups", ctypes.c_uint64),
+                ("gpu_ns", ctypes.c_uint64)]
+
+
 class WireBatchInfo(ctypes.Structure):
     _fields_ = [("n_messages", ctypes.c_uint64), ("deployment_id", ctypes.c_uint64),
                 ("source_address_len", ctypes.c_uint64), ("bin_ver", ctypes.c_uint32),
@@ -530,6 +540,8 @@ SIGNATURES = {
     "hq_worker_config_changes": (ctypes.c_int, [_vp, ctypes.c_uint64, _vp,
                                                 ctypes.POINTER(ConfigOutput)]),
     "hq_worker_readback_count": (ctypes.c_int, [_vp, _u64p]),
+    "hq_worker_get_groups": (ctypes.c_int, [_vp, ctypes.c_uint64, _vp, _vp]),
+    "hq_worker_set_groups": (ctypes.c_int, [_vp, ctypes.c_uint64, _vp, _vp, _u64p]),
     "hq_synth_commit_dev": (ctypes.c_int, [_vp, ctypes.POINTER(SynthSpec), ctypes.POINTER(CommitArgs)]),
     "hq_synth_commit_lag_dev": (ctypes.c_int, [_vp, ctypes.POINTER(SynthSpec),
                                                ctypes.POINTER(LagArgs), _vp]),
@@ -1755,6 +1767,57 @@ class Worker:
             buf = (ctypes.c_char * (count * dt.itemsize)).from_address(getattr(out, name))
             res[name] = np.frombuffer(buf, dt).copy() if copy else np.frombuffer(buf, dt)
         return res
+
+    def get_groups(self, handles=None, copy=True):
+        """hq_worker_get_groups: the state of the listed groups (uint32 handles, repeats allowed;
+        None: every handle in order) without a readback of the device state. Returns a dict:
+        'groups' (WORKER_GROUP_DTYPE, listed order), 'members' (MEMBER_DTYPE, group i's at
+        member_offsets[i] : member_offsets[i + 1], in the caller's order), 'member_offsets',
+        'reads' (READ_STATUS_DTYPE, queue order), 'read_offsets', 'granted' / 'rejected' (uint16
+        per group: bit i = member i of the group's list holds a recorded grant / rejection),
+        'read_confirmed' (uint16 per entry of 'reads': the members that acknowledged the ctx),
+        'gpu_ns'. With copy=False the arrays are views of the worker's buffers, valid until its
+        next get_groups call."""
+        if handles is None:
+            n, gp = self.group_count(), None
+        else:
+            handles = np.ascontiguousarray(handles, np.uint32)
+            n, gp = len(handles), _p(handles) if len(handles) else None
+        out = GroupsOutput()
+        self._check(lib.hq_worker_get_groups(self.h, n, gp, ctypes.byref(out)),
+                    "hq_worker_get_groups")
+        ng = out.n_groups
+
+        def arr(name, count, dt):
+            if count == 0:
+                return np.zeros(0, dt)
+            buf = (ctypes.c_char * (count * dt.itemsize)).from_address(getattr(out, name))
+            return np.frombuffer(buf, dt).copy() if copy else np.frombuffer(buf, dt)
+
+        res = {"gpu_ns": out.gpu_ns}
+        u2, u8 = np.dtype("<u2"), np.dtype("<u8")
+        res["member_offsets"] = arr("member_offsets", ng + 1, u8) if ng else np.zeros(1, u8)
+        res["read_offsets"] = arr("read_offsets", ng + 1, u8) if ng else np.zeros(1, u8)
+        nm, nr = int(res["member_offsets"][-1]), int(res["read_offsets"][-1])
+        for name, count, dt in (("groups", ng, WORKER_GROUP_DTYPE), ("members", nm, MEMBER_DTYPE),
+                                ("reads", nr, READ_STATUS_DTYPE), ("granted", ng, u2),
+                                ("rejected", ng, u2), ("read_confirmed", nr, u2)):
+            res[name] = arr(name, count, dt)
+        return res
+
+    def set_groups(self, groups, members) -> int:
+        """hq_worker_set_groups: hq_worker_set_group for every listed group (WORKER_GROUP_DTYPE
+        records, members of consecutive groups back to back), all validated before any is
+        changed; a device worker writes them with one kernel and reads nothing back. Returns
+        the call's gpu_ns (0 on a host worker)."""
+        groups = np.ascontiguousarray(groups, WORKER_GROUP_DTYPE)
+        members = np.ascontiguousarray(members, MEMBER_DTYPE)
+        assert int(groups["n_members"].sum()) == len(members)
+        ns = ctypes.c_uint64(0)
+        self._check(lib.hq_worker_set_groups(self.h, len(groups), _p(groups) if len(groups) else None,
+                                             _p(members) if len(members) else None,
+                                             ctypes.byref(ns)), "hq_worker_set_groups")
+        return ns.value
 
     def readback_count(self) -> int:
         """hq_worker_readback_count: how often the device-resident state was copied back."""

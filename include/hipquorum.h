@@ -1699,6 +1699,54 @@ int hq_worker_config_changes(hq_worker *w, uint64_t n, const hq_config_change *c
  * for a host worker): what a caller watches to keep a path free of readbacks. */
 int hq_worker_readback_count(hq_worker *w, uint64_t *n);
 
+/* ---------------------------------------------------------------- listed groups ------------- */
+/*
+ * The state of listed groups fetched from, and written to, the worker's quorum state where it
+ * lives: what a caller needs to take a suspended group over with the CPU raft (a step's fallback,
+ * HQ_CC_FALLBACK) and to hand it back, without hq_worker_get_group / _set_group's copy of the whole
+ * device state. A device worker moves one packed 768-byte record per listed group with one small
+ * kernel (hq_groups.hip: k_groups_gather into pinned host memory, k_groups_scatter from it);
+ * nothing is read back, the host mirror is neither refreshed nor marked, and
+ * hq_worker_readback_count does not move. A host worker gives the same output from its own
+ * records. Additions to ABI 21 (new symbols only); hq_worker_get_group, _set_group and _add_group
+ * keep their behaviour.
+ *
+ * hq_worker_get_groups: `handles` may repeat and come in any order; NULL means handles 0 .. n - 1.
+ * Queued hq_worker_add_group / _set_group uploads are flushed first. Group i of the output is
+ * handles[i], as hq_worker_get_group fills it; its members in the caller's order (the order of
+ * add / set, of get_group, of the heartbeat word's bits), its pending ReadIndex queue in queue
+ * order. The three masks are in the caller's terms too: bit i = member i of the group's list.
+ * granted / rejected: the members holding a recorded grant / rejection (r.votes,
+ * raft.go:1062-1080; a candidate's own vote included); read_confirmed, one per entry of `reads`:
+ * the members that acknowledged the ctx (readStatus.confirmed, readindex.go:21-26), its popcount
+ * the entry's n_confirmed. HQ_E_INVAL, before anything is queued: a NULL worker or output, an
+ * unknown handle, a host worker's group of more than 16 members (no 16-bit mask holds its list).
+ * HQ_E_STATE: a resident record does not match the host's structure (internal). n = 0 is HQ_OK
+ * with an empty output. The arrays are owned by the worker and valid until its next
+ * hq_worker_get_groups or close.
+ *
+ * hq_worker_set_groups: group i's members follow group i - 1's in `members`, as for
+ * hq_worker_add_groups; per group exactly hq_worker_set_group (validation, read queue and votes
+ * cleared, a candidate holds its own vote, the suspension lifted, a group that outgrew its member
+ * range moves to the pool's end, the route row untouched). All groups are validated before any is
+ * changed: an unknown cluster, a cluster listed twice or any invalid group is HQ_E_INVAL with
+ * nothing applied. *gpu_ns (may be NULL) as hq_groups_output's. n = 0 is HQ_OK.
+ */
+typedef struct hq_groups_output {
+    const hq_worker_group *groups;     /* [n_groups], listed order */
+    const hq_member *members;          /* group i: members[member_offsets[i] .. member_offsets[i + 1]) */
+    const uint64_t *member_offsets;    /* [n_groups + 1] */
+    const hq_read_status *reads;       /* group i: reads[read_offsets[i] .. read_offsets[i + 1]) */
+    const uint64_t *read_offsets;      /* [n_groups + 1] */
+    const uint16_t *granted, *rejected;/* [n_groups] */
+    const uint16_t *read_confirmed;    /* one per entry of `reads` */
+    uint64_t n_groups;
+    uint64_t gpu_ns;                   /* device workers: GPU time between the call's events, else 0 */
+} hq_groups_output;
+int hq_worker_get_groups(hq_worker *w, uint64_t n, const uint32_t *handles, hq_groups_output *out);
+int hq_worker_set_groups(hq_worker *w, uint64_t n, const hq_worker_group *groups,
+                         const hq_member *members, uint64_t *gpu_ns);
+
 /* ---------------------------------------------------------------- synthetic inputs ---------- */
 
 /*

@@ -116,6 +116,83 @@ func (x *Worker) SetGroup(g *GroupState, members []Member) error {
 	return x.err(C.hq_worker_set_group(x.w, g, mp))
 }
 
+// GroupsOutput is the state of the groups listed to GetGroups (hq_groups_output). The arrays live
+// in the worker's buffers and are valid until its next GetGroups call; the last step's Output
+// stays valid.
+type GroupsOutput struct {
+	c C.hq_groups_output
+}
+
+// GetGroups fetches the state of the listed groups (worker handles, repeats allowed; nil: every
+// handle 0 .. n-1 in order) in their state after every earlier step: what the CPU raft needs to
+// take over the groups of FallbackClusters or of a ConfigFallback. A device worker gathers one
+// packed record per listed group with one small kernel; nothing else of its state crosses the link
+// and its readback count does not move.
+func (x *Worker) GetGroups(handles []uint32, n int) (*GroupsOutput, error) {
+	o := &GroupsOutput{}
+	var hp *C.uint32_t
+	if handles != nil {
+		n = len(handles)
+		if n > 0 {
+			hp = (*C.uint32_t)(unsafe.Pointer(&handles[0]))
+		}
+	}
+	if rc := C.hq_worker_get_groups(x.w, C.uint64_t(n), hp, &o.c); rc != C.HQ_OK {
+		return nil, x.err(rc)
+	}
+	return o, nil
+}
+
+// Len is the number of listed groups, GPUNanos the HIP-event time of the call (0 on a host worker).
+func (o *GroupsOutput) Len() int         { return int(o.c.n_groups) }
+func (o *GroupsOutput) GPUNanos() uint64 { return uint64(o.c.gpu_ns) }
+
+// Group returns listed group i: its record, its members in the AddGroup / SetGroup order, and the
+// members holding a recorded grant and a recorded rejection (bit j = members[j]).
+func (o *GroupsOutput) Group(i int) (g GroupState, members []Member, granted, rejected uint16) {
+	n := int(o.c.n_groups)
+	g = unsafe.Slice(o.c.groups, n)[i]
+	mo := unsafe.Slice((*uint64)(unsafe.Pointer(o.c.member_offsets)), n+1)
+	if mo[n] != 0 {
+		members = unsafe.Slice(o.c.members, int(mo[n]))[mo[i]:mo[i+1]]
+	}
+	granted = unsafe.Slice((*uint16)(unsafe.Pointer(o.c.granted)), n)[i]
+	rejected = unsafe.Slice((*uint16)(unsafe.Pointer(o.c.rejected)), n)[i]
+	return g, members, granted, rejected
+}
+
+// Reads returns listed group i's pending ReadIndex queue in queue order, and per entry the members
+// that acknowledged its ctx (bit j = members[j]; readStatus.confirmed, readindex.go:21-26).
+func (o *GroupsOutput) Reads(i int) (reads []C.hq_read_status, confirmed []uint16) {
+	n := int(o.c.n_groups)
+	ro := unsafe.Slice((*uint64)(unsafe.Pointer(o.c.read_offsets)), n+1)
+	if ro[i] == ro[i+1] {
+		return nil, nil
+	}
+	reads = unsafe.Slice(o.c.reads, int(ro[n]))[ro[i]:ro[i+1]]
+	confirmed = unsafe.Slice((*uint16)(unsafe.Pointer(o.c.read_confirmed)), int(ro[n]))[ro[i]:ro[i+1]]
+	return reads, confirmed
+}
+
+// SetGroups re-syncs the listed groups from the CPU raft, each exactly as SetGroup does (read
+// queue and votes cleared, the suspension lifted); members holds the groups' members back to back.
+// Every group is validated before any is changed. A device worker writes the groups with one small
+// kernel and reads nothing back. Returns the HIP-event time of the call (0 on a host worker).
+func (x *Worker) SetGroups(groups []GroupState, members []Member) (uint64, error) {
+	if len(groups) == 0 {
+		return 0, nil
+	}
+	var mp *C.hq_member
+	if len(members) > 0 {
+		mp = &members[0]
+	}
+	var ns C.uint64_t
+	if rc := C.hq_worker_set_groups(x.w, C.uint64_t(len(groups)), &groups[0], mp, &ns); rc != C.HQ_OK {
+		return 0, x.err(rc)
+	}
+	return uint64(ns), nil
+}
+
 // Output is one step's results; the lists live in the worker's pinned buffers and are valid
 // until the worker's next step.
 type Output struct {
