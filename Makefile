@@ -5,22 +5,17 @@ HIPFLAGS ?= -O3 -std=c++17 -fPIC -Wall -Wno-unused-result --offload-arch=$(ARCH)
 CSRC := dragonboat_amd/csrc
 LIBDIR := dragonboat_amd/lib
 LIB := $(LIBDIR)/libhipquorum.so
-OBJS := $(LIBDIR)/hq_runtime.o $(LIBDIR)/hq_commit.o $(LIBDIR)/hq_commit_tiles.o \
-        $(LIBDIR)/hq_commit_lag.o $(LIBDIR)/hq_bits.o $(LIBDIR)/hq_ri_multi.o $(LIBDIR)/hq_synth.o \
-        $(LIBDIR)/hq_ingest.o $(LIBDIR)/hq_table.o $(LIBDIR)/hq_pack.o $(LIBDIR)/hq_worker.o \
-        $(LIBDIR)/hq_wire.o $(LIBDIR)/hq_stream.o $(LIBDIR)/hq_jobs.o $(LIBDIR)/hq_dstep.o \
-        $(LIBDIR)/hq_dstep_step.o $(LIBDIR)/hq_dstep_layout.o $(LIBDIR)/hq_dstep_run.o \
-        $(LIBDIR)/hq_engine.o $(LIBDIR)/hq_wire_frame.o $(LIBDIR)/hq_wire_dev.o \
-        $(LIBDIR)/hq_heartbeat.o $(LIBDIR)/hq_heartbeat_wire.o $(LIBDIR)/hq_wire_frame_dev.o \
-        $(LIBDIR)/hq_config.o $(LIBDIR)/hq_groups.o
 SRCS := $(CSRC)/hq_runtime.hip $(CSRC)/hq_commit.hip $(CSRC)/hq_commit_tiles.hip \
         $(CSRC)/hq_commit_lag.hip $(CSRC)/hq_bits.hip $(CSRC)/hq_ri_multi.hip $(CSRC)/hq_synth.hip \
         $(CSRC)/hq_ingest.hip $(CSRC)/hq_table.hip $(CSRC)/hq_pack.cpp $(CSRC)/hq_worker.cpp \
+        $(CSRC)/hq_worker_host.cpp $(CSRC)/hq_worker_dev.cpp $(CSRC)/hq_worker_hb.cpp \
+        $(CSRC)/hq_worker_lists.cpp \
         $(CSRC)/hq_wire.cpp $(CSRC)/hq_stream.cpp $(CSRC)/hq_jobs.cpp $(CSRC)/hq_dstep.hip \
         $(CSRC)/hq_dstep_step.hip $(CSRC)/hq_dstep_layout.hip $(CSRC)/hq_dstep_run.hip \
         $(CSRC)/hq_engine.hip $(CSRC)/hq_wire_frame.cpp $(CSRC)/hq_wire_dev.hip \
         $(CSRC)/hq_heartbeat.hip $(CSRC)/hq_heartbeat_wire.hip $(CSRC)/hq_wire_frame_dev.hip \
         $(CSRC)/hq_config.hip $(CSRC)/hq_groups.hip
+OBJS := $(patsubst $(CSRC)/%,$(LIBDIR)/%.o,$(basename $(SRCS)))
 DEPS := $(wildcard $(CSRC)/*.h) include/hipquorum.h
 CXX ?= g++
 CXXFLAGS ?= -O3 -std=c++17 -fPIC -pthread -Wall -Wextra

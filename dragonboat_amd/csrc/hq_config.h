@@ -1,5 +1,5 @@
 // hq_config.h — membership changes on the worker's quorum state (hq_worker_config_changes,
-// include/hipquorum.h "membership changes"), shared between hq_worker.cpp (plain C++: validation,
+// include/hipquorum.h "membership changes"), shared between hq_worker_lists.cpp (plain C++: validation,
 // the descriptors, the host worker's own edit and the mirror's), hq_config.hip (k_cfg_apply over a
 // device worker's resident records) and the stand-alone check of tests/test_config_ref.py. The
 // bitmap remaps and the position arithmetic below are the one source all three use.

@@ -1,5 +1,5 @@
 // hq_dstep.h — the device step engine of the step worker (hq_worker_open_ex with
-// HQ_WORKER_ON_DEVICE), shared between hq_worker.cpp (plain C++, the host side: state mirror,
+// HQ_WORKER_ON_DEVICE), shared between hq_worker_dev.cpp (plain C++, the host side: state mirror,
 // validation, outputs) and the engine's files (hq_dstep.hip, _step, _layout, _run). Internal.
 #pragma once
 
@@ -137,12 +137,12 @@ int hq_dstep_run_jobs(hq_dstep *const *ds, const hq_dstep_in *ins, hq_dstep_out 
                       uint32_t count);
 constexpr uint32_t kDStepMaxJobs = 64;
 
-// hq_worker.cpp, for hq_worker_step_jobs (hq_jobs.cpp): the jobs stepped through shared device
+// hq_worker_dev.cpp, for hq_worker_step_jobs (hq_jobs.cpp): the jobs stepped through shared device
 // launches when they allow it; kJobsNotFused (nothing done) when they do not
 constexpr int kJobsNotFused = 1 << 30;
 int hq_worker_step_jobs_fused(hq_step_job *jobs, uint32_t count);
 
-// hq_worker.cpp, for the wire's device mode (hq_wire_dev.hip): a device worker's context (NULL:
+// hq_worker.cpp and hq_worker_dev.cpp, for the wire's device mode (hq_wire_dev.hip): a device worker's context (NULL:
 // not a device worker), the cluster ids of handles [h0, h0 + n), and hq_worker_step over rows that
 // are already on the device (hq_dstep_in::on_device; queued on the context's stream behind
 // whatever produced them)

@@ -1,6 +1,6 @@
 // hq_groups.h — the state of listed groups fetched from and written to a worker's quorum state
 // (hq_worker_get_groups / hq_worker_set_groups, include/hipquorum.h "listed groups"), shared
-// between hq_worker.cpp (plain C++: both calls' host side), hq_groups.hip (k_groups_gather /
+// between hq_worker_lists.cpp (plain C++: both calls' host side), hq_groups.hip (k_groups_gather /
 // k_groups_scatter over a device worker's resident records) and the stand-alone check of
 // tests/test_groups_ref.py. The packed record's layout, pack / unpack and the mapping of a slot
 // bitmap to list positions below are the one source all three use.

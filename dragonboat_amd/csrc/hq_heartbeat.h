@@ -1,5 +1,5 @@
 // hq_heartbeat.h — the leader heartbeat broadcast of a device worker (hq_worker_heartbeats),
-// shared between hq_worker.cpp (plain C++: the flush, the checks, the host worker's own form) and
+// shared between hq_worker_hb.cpp (plain C++: the flush, the checks, the host worker's own form) and
 // hq_heartbeat.hip (the kernels and their buffers). Internal to libhipquorum.so.
 #pragma once
 

@@ -1,6 +1,6 @@
 // hq_heartbeat_wire.h — the Heartbeat marshaller of hq_worker_heartbeat_batches: one message and
 // the MessageBatch trailer, written with hq_wire_codec.h's writers (as hq_wire_encode_batch writes
-// any message). One source for the host worker (hq_worker.cpp), the kernels
+// any message). One source for the host worker (hq_worker_hb.cpp), the kernels
 // (hq_heartbeat_wire.hip) and the stand-alone sanitizer program of
 // tests/test_heartbeat_wire_host.py, so the functions run on the CPU under sanitizers before they
 // run on the GPU. No table, no array indexed by a variable: the kernels keep everything in

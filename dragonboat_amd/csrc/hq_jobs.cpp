@@ -10,6 +10,7 @@
 
 #include "../../include/hipquorum.h"
 #include "hq_dstep.h"
+#include "hq_guard.h"
 
 namespace {
 
@@ -32,6 +33,9 @@ class Pool {
 
     int run(hq_step_job *jobs, uint32_t count) {
         std::lock_guard<std::mutex> call(call_mu_);      // one batch of jobs at a time
+        // (a spawn that fails throws before the batch is posted: threads_ holds only started
+        // threads, each parked on cv_, and the next call grows the pool again)
+        threads_.reserve(count - 1);
         while (threads_.size() + 1 < count) {
             const size_t k = threads_.size();
             threads_.emplace_back([this, k] { loop(k); });
@@ -87,16 +91,20 @@ Pool &pool() {
 
 }  // namespace
 
+// (an exception of the call itself — the pool's growth, a thread's spawn — belongs to no job: the
+// code alone is returned; each job's own entry keeps its worker's message)
 extern "C" int hq_worker_step_jobs(hq_step_job *jobs, uint32_t count) {
-    if (!jobs && count) return HQ_E_INVAL;
-    if (count == 0) return HQ_OK;
-    for (uint32_t i = 0; i < count; ++i) {             // a worker is not thread-safe
-        jobs[i].rc = HQ_OK;
-        for (uint32_t k = 0; k < i; ++k)
-            if (jobs[k].worker == jobs[i].worker) return HQ_E_INVAL;
-    }
-    if (count == 1) return run_job(jobs[0]);
-    const int f = hq_worker_step_jobs_fused(jobs, count);
-    if (f != kJobsNotFused) return f;
-    return pool().run(jobs, count);
+    return hq::guard("hq_worker_step_jobs", [](int, const std::string &) {}, [&] {
+        if (!jobs && count) return HQ_E_INVAL;
+        if (count == 0) return HQ_OK;
+        for (uint32_t i = 0; i < count; ++i) {         // a worker is not thread-safe
+            jobs[i].rc = HQ_OK;
+            for (uint32_t k = 0; k < i; ++k)
+                if (jobs[k].worker == jobs[i].worker) return HQ_E_INVAL;
+        }
+        if (count == 1) return run_job(jobs[0]);
+        const int f = hq_worker_step_jobs_fused(jobs, count);
+        if (f != kJobsNotFused) return f;
+        return pool().run(jobs, count);
+    });
 }

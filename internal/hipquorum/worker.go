@@ -218,7 +218,8 @@ func (x *Worker) Step(groups []uint32, offsets []uint64, events []C.hq_event) (*
 
 // StreamBuf is one step's input as an event stream in pinned C memory: per event a header byte
 // and the LEB128 varints of the fields its handler reads (include/hipquorum.h "event streams"),
-// per node one size word (events | bytes << 16; the sized form of hq_step_stream).
+// per node one 2-byte byte count (hq_step_stream.sizes16, the bytes-only sized form: the engine
+// counts the events from the bytes).
 type StreamBuf struct {
 	Groups  []uint32 // worker handles, or nil: every handle 0 .. len(Sizes)-1 in order
 	Sizes   []uint16 // per node its byte count (hq_step_stream.sizes16: the engine counts events)

@@ -1,5 +1,5 @@
 """hq_worker_config_changes on device and host workers (dragonboat_amd/csrc/hq_config.hip,
-hq_worker.cpp): membership changes applied where the quorum state lives. Expected values are the
+hq_worker_lists.cpp): membership changes applied where the quorum state lives. Expected values are the
 Python restatement of raft.go:1136-1199, 1540-1559 (tests/config_ref.py) over Worker.get_group,
 the reference's tables (tests/golden/config_change_kats.json) and, for the steps after a change,
 a fresh oracle (oracle/qref_step.c) built from the restatement's post-change state."""

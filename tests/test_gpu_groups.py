@@ -1,5 +1,5 @@
 """hq_worker_get_groups / hq_worker_set_groups on device and host workers
-(dragonboat_amd/csrc/hq_groups.hip, hq_worker.cpp): the state of listed groups fetched and resumed
+(dragonboat_amd/csrc/hq_groups.hip, hq_worker_lists.cpp): the state of listed groups fetched and resumed
 where it lives, without a readback. Expected values never come from the new calls: they are
 Worker.get_group (the full readback, taken AFTER the new call ran against a stale mirror),
 Worker.set_group one group at a time on a twin worker, what the test itself sent (the masks), and

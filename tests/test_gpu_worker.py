@@ -1,4 +1,4 @@
-"""The GPU step worker (hq_worker_*, dragonboat_amd/csrc/hq_worker.cpp) against the sequential
+"""The GPU step worker (hq_worker_*, dragonboat_amd/csrc/hq_worker*.cpp) against the sequential
 step oracle (oracle/qref_step.c): the reference's raft-level tests restated as step scenarios,
 then random multi-step differential runs over thousands of groups. Every quorum decision of the
 worker is a kernel launch; results must be identical to the reference processing the same events
