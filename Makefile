@@ -10,7 +10,7 @@ SRCS := $(CSRC)/hq_runtime.hip $(CSRC)/hq_commit.hip $(CSRC)/hq_commit_tiles.hip
         $(CSRC)/hq_ingest.hip $(CSRC)/hq_table.hip $(CSRC)/hq_pack.cpp $(CSRC)/hq_worker.cpp \
         $(CSRC)/hq_worker_host.cpp $(CSRC)/hq_worker_dev.cpp $(CSRC)/hq_worker_hb.cpp \
         $(CSRC)/hq_worker_lists.cpp \
-        $(CSRC)/hq_wire.cpp $(CSRC)/hq_stream.cpp $(CSRC)/hq_jobs.cpp $(CSRC)/hq_dstep.hip \
+        $(CSRC)/hq_wire.cpp $(CSRC)/hq_stream.cpp $(CSRC)/hq_stream16.cpp $(CSRC)/hq_jobs.cpp $(CSRC)/hq_dstep.hip \
         $(CSRC)/hq_dstep_step.hip $(CSRC)/hq_dstep_layout.hip $(CSRC)/hq_dstep_run.hip \
         $(CSRC)/hq_engine.hip $(CSRC)/hq_wire_frame.cpp $(CSRC)/hq_wire_dev.hip \
         $(CSRC)/hq_heartbeat.hip $(CSRC)/hq_heartbeat_wire.hip $(CSRC)/hq_wire_frame_dev.hip \
@@ -44,8 +44,6 @@ oracle:
 # tuning variants (one library each, for A/B runs via HQ_LIB_PATH, tools/ab_libs.sh):
 #   lib_ivN    records per lane of the table ingest kernels
 #   lib_ingnostore / lib_ingnoload the grouped table ingest without its table stores / loads (timing probes: wrong output)
-#   lib_encspawn the threaded event encoder spawning its threads per call (before the task pool)
-#   lib_encprof the threaded encoder's per-range start / barrier arrival per call (stderr)
 #   lib_engprof the engine's per-workgroup clocks and tile counts (hq_engine_wgprof; tools/engine_wgprof.py)
 define variant
 	@mkdir -p $(dir $@)
@@ -58,14 +56,10 @@ clean:
 	rm -rf $(LIBDIR) oracle/build
 
 .PHONY: all oracle clean
-tools/lib_encspawn/libhipquorum.so: $(SRCS) $(DEPS)
-	$(call variant,-DHQ_ENCODE_SPAWN)
 tools/lib_ingnostore/libhipquorum.so: $(SRCS) $(DEPS)
 	$(call variant,-DHQ_INGEST_NOSTORE)
 tools/lib_ingnoload/libhipquorum.so: $(SRCS) $(DEPS)
 	$(call variant,-DHQ_INGEST_NOLOAD)
-tools/lib_encprof/libhipquorum.so: $(SRCS) $(DEPS)
-	$(call variant,-DHQ_ENC_PROF)
 tools/lib_engprof/libhipquorum.so: $(SRCS) $(DEPS)
 	$(call variant,-DHQ_ENGINE_WGPROF)
 # binned-ingest A/B (tools/ab_bin.sh): kernel parts removed (HQ_BIN_AB) or smaller regions

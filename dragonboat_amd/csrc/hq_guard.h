@@ -1,11 +1,14 @@
-// hq_guard.h — the one exception guard of the step worker's C entries (hq_worker*.cpp,
-// hq_jobs.cpp): no C++ exception crosses the C-ABI. An entry's body runs inside hq::guard; what
+// hq_guard.h — the one exception guard of the C entries of the step worker (hq_worker*.cpp,
+// hq_jobs.cpp), the wire (hq_wire.cpp) and the event stream (hq_stream*.cpp, hq_task_pool.h): no
+// C++ exception crosses the C-ABI. An entry's body runs inside hq::guard; what
 // it returns is the entry's code, what it throws becomes one:
 //   std::bad_alloc, std::length_error   HQ_E_NOMEM  "<entry>: out of memory"
 //   std::system_error                   HQ_E_NOMEM  "<entry>: <what()>"
 //   anything else                       HQ_E_STATE  "<entry>: unexpected exception"
 // `record(code, message)` keeps the message where the entry's caller reads it (a worker's
-// hq_worker_last_error). Nothing but the standard library and the error codes.
+// hq_worker_last_error, a wire's hq_wire_last_error); an entry without a handle has nowhere to
+// keep one and uses the form without `record`: the code alone. Nothing but the standard library
+// and the error codes.
 #pragma once
 #include <new>
 #include <stdexcept>
@@ -39,6 +42,11 @@ int guard(const char *entry, Record &&record, Body &&body) noexcept {
     } catch (...) {
         return guard_report(entry, "unexpected exception", HQ_E_STATE, record);
     }
+}
+
+template <class Body>
+int guard(const char *entry, Body &&body) noexcept {
+    return guard(entry, [](int, const std::string &) {}, body);
 }
 
 }  // namespace hq

@@ -94,7 +94,7 @@ Pool &pool() {
 // (an exception of the call itself — the pool's growth, a thread's spawn — belongs to no job: the
 // code alone is returned; each job's own entry keeps its worker's message)
 extern "C" int hq_worker_step_jobs(hq_step_job *jobs, uint32_t count) {
-    return hq::guard("hq_worker_step_jobs", [](int, const std::string &) {}, [&] {
+    return hq::guard("hq_worker_step_jobs", [&] {
         if (!jobs && count) return HQ_E_INVAL;
         if (count == 0) return HQ_OK;
         for (uint32_t i = 0; i < count; ++i) {         // a worker is not thread-safe

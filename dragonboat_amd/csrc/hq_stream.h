@@ -1,5 +1,5 @@
-// hq_stream.h — internal: the event-stream encoder shared by hq_stream.cpp (rows, compact
-// records) and hq_wire.cpp (events decoded from the wire). Internal to libhipquorum.so.
+// hq_stream.h — internal: the event-stream encoder shared by hq_stream.cpp (rows) and
+// hq_wire.cpp (events decoded from the wire). Internal to libhipquorum.so.
 #pragma once
 
 #include <cstdint>
@@ -34,6 +34,18 @@ inline hq_event to_event(const WireEvent &r) {
     e.hint_high = r.hint_high;
     e.reject = r.reject;
     return e;
+}
+
+// a row's fields into a wire event (to_event's inverse; key and cat are the wire's own)
+inline void from_event(WireEvent &r, const hq_event &e) {
+    r.kind = (uint8_t)e.kind;
+    r.reject = e.reject != 0;
+    r.type = e.type;
+    r.from = e.from;
+    r.term = e.term;
+    r.log_index = e.log_index;
+    r.hint = e.hint;
+    r.hint_high = e.hint_high;
 }
 
 // one group's events ev[0 .. n) encoded at p as hq_events_encode does (its runs and repeat

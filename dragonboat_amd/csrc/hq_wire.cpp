@@ -12,12 +12,22 @@
 // (Message.MarshalTo raft.pb.go:2232-2300, MessageBatch.MarshalTo :2417-2445); the decoder
 // accepts any valid proto2 encoding of them (fields in any order, unknown fields skipped, as
 // Message.Unmarshal raft.pb.go:4831 / raft_optimized.go:654 do).
+//
+// No exception leaves an entry. Every int-returning entry with a wire runs its body in `guarded`
+// (hq_guard.h: HQ_E_INVAL for no wire, an exception's code with "<entry>: out of memory" and the
+// like in hq_wire_last_error), those that reach hq_wire_dev.hip through hq_wire_dev_* included: an
+// exception from there is caught here. hq_wire_decode_batch and hq_wire_encode_batch have no
+// handle and answer with the code alone. hq_wire_open allocates with new (std::nothrow);
+// hq_wire_close and hq_wire_last_error return no code and allocate nothing: the three stay bare.
+// What a caught exception leaves behind is said at each entry.
+#include <algorithm>
 #include <new>
 #include <string>
 #include <utility>
 #include <vector>
 
 #include "../../include/hipquorum.h"
+#include "hq_guard.h"
 #include "hq_stream.h"
 #include "hq_wire_codec.h"
 #include "hq_wire_dev.h"
@@ -104,6 +114,18 @@ class ClusterIndex {
         if (!slots_.empty()) __builtin_prefetch(&slots_[hash(id) & (slots_.size() - 1)]);
     }
     size_t size() const { return used_.size() + has_empty_; }
+    // The ids added since `mark()` leave again, last first: with linear probing the table is then
+    // slot for slot what it was (no earlier id's probe passed the slot of a later one; a rehash
+    // keeps the order of insertion), but for its capacity.
+    struct Mark {
+        size_t used;
+        bool has_empty;
+    };
+    Mark mark() const { return Mark{used_.size(), has_empty_}; }
+    void rollback(Mark m) {
+        for (; used_.size() > m.used; used_.pop_back()) slots_[used_.back()].key = kEmpty;
+        has_empty_ = m.has_empty;
+    }
     // the index of id, inserting next if new (*fresh = true)
     uint32_t find_or_add(uint64_t id, uint32_t next, bool *fresh) {
         if ((used_.size() + 1) * 2 > slots_.size()) rehash(slots_.empty() ? 1024 : slots_.size() * 2);
@@ -124,9 +146,9 @@ class ClusterIndex {
                     *fresh = false;
                     return empty_val_;
                 }
+                used_.push_back((uint32_t)i);     // (first: when it throws, the slot is still empty)
                 slots_[i].key = id;
                 slots_[i].val = next;
-                used_.push_back((uint32_t)i);
                 *fresh = true;
                 return next;
             }
@@ -177,7 +199,8 @@ struct hq_wire {
     std::vector<hq_event> events;
     std::vector<uint64_t> boffsets;    // hq_wire_step_stream
     std::vector<uint8_t> bytes;
-    std::vector<uint32_t> cnt, perm, pos;   // hq_wire_step_sized's counting sort
+    std::vector<uint32_t> cnt, perm, pos;   // the steps' counting sort (scatter)
+    std::vector<uint32_t> handle;      // hq_wire_step_input: each cluster's handle
     std::vector<uint32_t> kcnt;        // attached: the records queued per handle (at h + 1)
     // the device mode (hq_wire_attach_device): batches are framed here and queued there; recs
     // holds the local events only
@@ -188,19 +211,72 @@ struct hq_wire {
     uint64_t n_rejected = 0;
     uint64_t dev_queued = 0;           // messages queued on the device side
 
-    void count_key(uint32_t k) {
+    void count_key(uint32_t k, uint32_t m = 1) {
         if ((size_t)k + 2 > kcnt.size()) kcnt.resize(std::max<size_t>((size_t)k + 2, 2 * kcnt.size()), 0);
-        kcnt[(size_t)k + 1]++;
+        kcnt[(size_t)k + 1] += m;
     }
     static constexpr uint32_t kNoKey = UINT32_MAX;   // a record of a cluster the worker does not run
-    // records r0.. leave the queue (a batch dropped after its decode)
-    void drop_from(size_t r0) {
-        if (worker)
-            for (size_t i = r0; i < recs.size(); ++i)
-                if (recs[i].key != kNoKey) kcnt[(size_t)recs[i].key + 1]--;
-        recs.resize(r0);
+    std::vector<Rec> grp;              // hq_wire_step_sized: one group's events
+
+    // hq_wire_add_batch and hq_wire_add_locals are all or nothing: unless `keep` is set, leaving
+    // the scope (an exception, a refusal) puts recs, kcnt, clusters, cluster_index and stats back
+    // to what they were when the entry began. Cluster ids newly cached in handle_of stay: a cache
+    // of facts that do not change. Nothing in it allocates.
+    struct Undo {
+        hq_wire &w;
+        const size_t r0, c0;
+        const ClusterIndex::Mark i0;
+        const hq_wire_stats s0;
+        size_t counted = 0;            // attached: kcnt holds the keys of recs[r0 .. r0 + counted)
+        bool keep = false;
+        explicit Undo(hq_wire &x)
+            : w(x), r0(x.recs.size()), c0(x.clusters.size()), i0(x.cluster_index.mark()), s0(x.stats) {}
+        // the records since r0 leave the queue (also: a batch dropped after its decode); kept
+        // out of line, so that the entries' hot loops are what they were without it
+        __attribute__((noinline)) void drop() {
+            for (size_t i = r0; i < r0 + counted; ++i)
+                if (w.recs[i].key != kNoKey) w.kcnt[(size_t)w.recs[i].key + 1]--;
+            counted = 0;
+            w.recs.resize(r0);
+            w.clusters.resize(c0);
+            w.cluster_index.rollback(i0);
+        }
+        ~Undo() {
+            if (keep) return;
+            drop();
+            w.stats = s0;
+        }
+    };
+    // an entry that needs an empty queue
+    int need_empty(const char *entry) {
+        if (recs.empty() && !dev_queued) return HQ_OK;
+        return fail(HQ_E_STATE, std::string(entry) + ": events queued (reset first)");
     }
-    std::vector<Rec> grp;              //   and one group's events
+    // The tail of both attaches: the wire feeds `wk` from now on, through `d` in the device mode.
+    // Everything that can throw or refuse comes before it: this only switches (a fresh handle
+    // table and an emptied kcnt allocate nothing).
+    void attach_to(hq_worker *wk, hq_wire_dev *d) noexcept {
+        if (dev) hq_wire_dev_close(dev);
+        dev = d;
+        rejected = nullptr;
+        n_rejected = 0;
+        worker = wk;
+        handle_of = ClusterIndex();
+        kcnt.clear();
+    }
+    // The counts in cnt (key k's at k + 1) made offsets, and the queue scattered by them into
+    // perm: key k's records are perm[cnt[k] .. cnt[k + 1]), stable in arrival order. false (and
+    // nothing scattered) when the counts are not the queue's.
+    template <class KeyOf>
+    bool scatter(KeyOf key_of) {
+        const uint32_t nr = (uint32_t)recs.size();
+        for (size_t i = 1; i < cnt.size(); ++i) cnt[i] += cnt[i - 1];
+        if (cnt.back() != nr) return false;
+        perm.resize(nr);
+        pos.assign(cnt.begin(), cnt.end() - 1);
+        for (uint32_t i = 0; i < nr; ++i) perm[pos[key_of(recs[i])]++] = i;
+        return true;
+    }
 
     int fail(int code, const std::string &m) {
         err = m;
@@ -252,25 +328,43 @@ struct hq_wire {
     }
 };
 
+namespace {
+
+// A C entry of the wire: HQ_E_INVAL for no wire, else the body's code, or an exception's
+// (hq_guard.h) with its message in hq_wire_last_error.
+struct KeepError {                     // (a type of its own: one guard_report for all entries)
+    hq_wire *w;
+    void operator()(int code, const std::string &m) const { w->fail(code, m); }
+};
+template <class Body>
+int guarded(hq_wire *w, const char *entry, Body &&body) {
+    if (!w) return HQ_E_INVAL;
+    return hq::guard(entry, KeepError{w}, body);
+}
+
+}  // namespace
+
 extern "C" {
 
 int hq_wire_decode_batch(const uint8_t *bytes, size_t len, hq_wire_message *out, uint64_t cap,
                          uint64_t *count, hq_wire_batch_info *info) {
     if ((!bytes && len) || !count) return HQ_E_INVAL;
-    hq_wire_batch_info bi;
-    const int rc = hqw::walk_batch(
-        bytes, len, bi,
-        [&](size_t, size_t body, size_t n) {
-            hq_wire_message tmp;
-            hqw::error e;
-            hq_wire_message &dst = out && bi.n_messages < cap ? out[bi.n_messages] : tmp;
-            return hqw::decode_message(bytes + body, n, dst, e) ? HQ_OK : HQ_E_INVAL;
-        },
-        [] {});
-    *count = bi.n_messages;
-    if (rc) return rc;
-    if (info) *info = bi;
-    return *count > cap && out ? HQ_E_STATE : HQ_OK;
+    return hq::guard("hq_wire_decode_batch", [&] {
+        hq_wire_batch_info bi;
+        const int rc = hqw::walk_batch(
+            bytes, len, bi,
+            [&](size_t, size_t body, size_t n) {
+                hq_wire_message tmp;
+                hqw::error e;
+                hq_wire_message &dst = out && bi.n_messages < cap ? out[bi.n_messages] : tmp;
+                return hqw::decode_message(bytes + body, n, dst, e) ? HQ_OK : HQ_E_INVAL;
+            },
+            [] {});
+        *count = bi.n_messages;
+        if (rc) return rc;
+        if (info) *info = bi;
+        return *count > cap && out ? HQ_E_STATE : HQ_OK;
+    });
 }
 
 // The sending node's side (bench and tests): MessageBatch.MarshalTo (raft.pb.go:2417-2445) over
@@ -280,23 +374,25 @@ int hq_wire_encode_batch(const hq_wire_message *msgs, uint64_t n, uint64_t deplo
                          const uint8_t *source, size_t source_len, uint8_t *out, uint64_t cap,
                          uint64_t *len) {
     if ((n && !msgs) || !len || (source_len && !source) || (cap && !out)) return HQ_E_INVAL;
-    uint8_t *p = out, *const end = out + cap;
-    for (uint64_t i = 0; i < n; ++i) {
-        const hq_wire_message &m = msgs[i];
-        if (m.n_entries) return HQ_E_INVAL;      // (entries are not marshalled here)
-        const uint64_t reject = m.ev.reject ? 1u : 0u;
-        const uint64_t size = hqw::body_size(m.ev.type, m.to, m.ev.from, m.cluster_id, m.ev.term,
-                                             m.log_term, m.ev.log_index, m.commit, reject, m.ev.hint,
-                                             m.ev.hint_high);
-        if ((uint64_t)(end - p) < size + 1 + hqw::vlen(size)) return HQ_E_STATE;
-        p = hqw::put_field(p, 0x0a, size);        // requests (1), length-delimited
-        p = hqw::put_body(p, m.ev.type, m.to, m.ev.from, m.cluster_id, m.ev.term, m.log_term,
-                          m.ev.log_index, m.commit, reject, m.ev.hint, m.ev.hint_high);
-    }
-    if ((uint64_t)(end - p) < 1 + 10 + 1 + 10 + source_len + 1 + 10) return HQ_E_STATE;
-    p = hqw::put_trailer(p, deployment_id, source, source_len);
-    *len = (uint64_t)(p - out);
-    return HQ_OK;
+    return hq::guard("hq_wire_encode_batch", [&] {
+        uint8_t *p = out, *const end = out + cap;
+        for (uint64_t i = 0; i < n; ++i) {
+            const hq_wire_message &m = msgs[i];
+            if (m.n_entries) return HQ_E_INVAL;      // (entries are not marshalled here)
+            const uint64_t reject = m.ev.reject ? 1u : 0u;
+            const uint64_t size = hqw::body_size(m.ev.type, m.to, m.ev.from, m.cluster_id, m.ev.term,
+                                                 m.log_term, m.ev.log_index, m.commit, reject,
+                                                 m.ev.hint, m.ev.hint_high);
+            if ((uint64_t)(end - p) < size + 1 + hqw::vlen(size)) return HQ_E_STATE;
+            p = hqw::put_field(p, 0x0a, size);        // requests (1), length-delimited
+            p = hqw::put_body(p, m.ev.type, m.to, m.ev.from, m.cluster_id, m.ev.term, m.log_term,
+                              m.ev.log_index, m.commit, reject, m.ev.hint, m.ev.hint_high);
+        }
+        if ((uint64_t)(end - p) < 1 + 10 + 1 + 10 + source_len + 1 + 10) return HQ_E_STATE;
+        p = hqw::put_trailer(p, deployment_id, source, source_len);
+        *len = (uint64_t)(p - out);
+        return HQ_OK;
+    });
 }
 
 int hq_wire_open(uint64_t deployment_id, hq_wire **out) {
@@ -314,70 +410,64 @@ void hq_wire_close(hq_wire *w) {
 
 const char *hq_wire_last_error(const hq_wire *w) { return w ? w->err.c_str() : ""; }
 
+// hq_wire_attach, hq_wire_attach_device: after an exception (or a refusal) the wire is attached
+// as it was: everything that can throw comes before the first field is switched (attach_to).
 int hq_wire_attach(hq_wire *w, hq_worker *worker) {
-    if (!w) return HQ_E_INVAL;
-    if (!w->recs.empty() || w->dev_queued)
-        return w->fail(HQ_E_STATE, "hq_wire_attach: events queued (reset first)");
-    if (w->dev) {                      // back from the device mode
-        hq_wire_dev_close(w->dev);
-        w->dev = nullptr;
-        w->rejected = nullptr;
-        w->n_rejected = 0;
-    }
-    w->worker = worker;
-    w->handle_of = ClusterIndex();
-    w->kcnt.clear();
-    return HQ_OK;
+    return guarded(w, "hq_wire_attach", [&] {
+        if (const int rc = w->need_empty("hq_wire_attach")) return rc;
+        w->attach_to(worker, nullptr);             // (back from the device mode, if in it)
+        return HQ_OK;
+    });
 }
 
 int hq_wire_attach_device(hq_wire *w, hq_worker *worker) {
-    if (!w) return HQ_E_INVAL;
-    if (!worker) return w->fail(HQ_E_INVAL, "hq_wire_attach_device: NULL worker");
-    if (!w->recs.empty() || w->dev_queued)
-        return w->fail(HQ_E_STATE, "hq_wire_attach_device: events queued (reset first)");
-    hq_wire_dev *dev = nullptr;
-    const int rc = hq_wire_dev_open(worker, &dev);
-    if (rc)
-        return w->fail(rc, rc == HQ_E_INVAL ? "hq_wire_attach_device: not a device worker "
-                                              "(HQ_WORKER_ON_DEVICE)"
-                                            : "hq_wire_attach_device: device buffers");
-    if (w->dev) hq_wire_dev_close(w->dev);
-    w->dev = dev;
-    w->rejected = nullptr;
-    w->n_rejected = 0;
-    w->worker = worker;
-    w->handle_of = ClusterIndex();
-    w->kcnt.clear();
-    return HQ_OK;
+    return guarded(w, "hq_wire_attach_device", [&] {
+        if (!worker) return w->fail(HQ_E_INVAL, "hq_wire_attach_device: NULL worker");
+        if (const int rc = w->need_empty("hq_wire_attach_device")) return rc;
+        hq_wire_dev *dev = nullptr;
+        const int rc = hq_wire_dev_open(worker, &dev);
+        if (rc)
+            return w->fail(rc, rc == HQ_E_INVAL ? "hq_wire_attach_device: not a device worker "
+                                                  "(HQ_WORKER_ON_DEVICE)"
+                                                : "hq_wire_attach_device: device buffers");
+        w->attach_to(worker, dev);
+        return HQ_OK;
+    });
 }
 
 int hq_wire_reset(hq_wire *w) {
-    if (!w) return HQ_E_INVAL;
-    if (w->dev) hq_wire_dev_reset(w->dev);
-    w->batch_calls = 0;
-    w->dev_queued = 0;
-    w->rejected = nullptr;
-    w->n_rejected = 0;
-    w->recs.clear();
-    std::fill(w->kcnt.begin(), w->kcnt.end(), 0u);
-    w->clusters.clear();
-    w->cluster_index.clear();
-    w->stats = hq_wire_stats{};
-    return HQ_OK;
+    return guarded(w, "hq_wire_reset", [&] {
+        if (w->dev) hq_wire_dev_reset(w->dev);
+        w->batch_calls = 0;
+        w->dev_queued = 0;
+        w->rejected = nullptr;
+        w->n_rejected = 0;
+        w->recs.clear();
+        std::fill(w->kcnt.begin(), w->kcnt.end(), 0u);
+        w->clusters.clear();
+        w->cluster_index.clear();
+        w->stats = hq_wire_stats{};
+        return HQ_OK;
+    });
 }
 
 int hq_wire_add_local(hq_wire *w, uint64_t cluster_id, const hq_event *events, uint64_t count) {
-    if (!w || (count && !events)) return HQ_E_INVAL;
-    const uint64_t off[2] = {0, count};
-    return hq_wire_add_locals(w, 1, &cluster_id, off, events);
+    return guarded(w, "hq_wire_add_local", [&] {
+        if (count && !events) return HQ_E_INVAL;
+        const uint64_t off[2] = {0, count};
+        return hq_wire_add_locals(w, 1, &cluster_id, off, events);
+    });
 }
 
-int hq_wire_add_locals(hq_wire *w, uint64_t n, const uint64_t *cluster_ids, const uint64_t *offsets,
-                       const hq_event *events) {
-    if (!w || (n && (!cluster_ids || !offsets))) return HQ_E_INVAL;
+// All or nothing: after an exception the queue, the per-handle counts, the clusters seen and the
+// stats are as before the call (hq_wire::Undo).
+static int add_locals(hq_wire *w, uint64_t n, const uint64_t *cluster_ids, const uint64_t *offsets,
+                      const hq_event *events) {
+    if (n && (!cluster_ids || !offsets)) return HQ_E_INVAL;
     if (n && offsets[n] > offsets[0] && !events) return HQ_E_INVAL;
     for (uint64_t c = 0; c < n; ++c) {
-        if (offsets[c + 1] < offsets[c]) return w->fail(HQ_E_INVAL, "hq_wire_add_locals: offsets decrease");
+        if (offsets[c + 1] < offsets[c])
+            return w->fail(HQ_E_INVAL, "hq_wire_add_locals: offsets decrease");
         for (uint64_t i = offsets[c]; i < offsets[c + 1]; ++i) {
             switch (events[i].kind) {
             case HQ_EV_READ: case HQ_EV_CHECK_QUORUM: case HQ_EV_ELECTION: case HQ_EV_PROPOSE: break;
@@ -385,6 +475,7 @@ int hq_wire_add_locals(hq_wire *w, uint64_t n, const uint64_t *cluster_ids, cons
             }
         }
     }
+    hq_wire::Undo undo(*w);
     for (uint64_t c = 0; c < n; ++c) {
         if (offsets[c + 1] == offsets[c]) continue;
         uint32_t k;
@@ -397,19 +488,20 @@ int hq_wire_add_locals(hq_wire *w, uint64_t n, const uint64_t *cluster_ids, cons
             Rec r{};
             r.key = k;
             r.cat = e.kind == HQ_EV_READ ? 0 : e.kind == HQ_EV_PROPOSE ? 3 : 2;
-            r.kind = (uint8_t)e.kind;
-            r.reject = e.reject != 0;
-            r.type = e.type;
-            r.from = e.from;
-            r.term = e.term;
-            r.log_index = e.log_index;
-            r.hint = e.hint;
-            r.hint_high = e.hint_high;
+            hqs::from_event(r, e);
             w->recs.push_back(r);
-            if (w->worker) w->count_key(k);
         }
+        if (!w->worker) continue;
+        w->count_key(k, (uint32_t)(offsets[c + 1] - offsets[c]));   // (the cluster's, at once)
+        undo.counted = w->recs.size() - undo.r0;
     }
+    undo.keep = true;
     return HQ_OK;
+}
+
+int hq_wire_add_locals(hq_wire *w, uint64_t n, const uint64_t *cluster_ids, const uint64_t *offsets,
+                       const hq_event *events) {
+    return guarded(w, "hq_wire_add_locals", [&] { return add_locals(w, n, cluster_ids, offsets, events); });
 }
 
 // The device mode: the batch framed (no message looked into), its own fields checked as below, its
@@ -431,52 +523,54 @@ static int add_batch_device(hq_wire *w, const uint8_t *bytes, size_t len) {
         rc = hq_wire_frame_batch(bytes, len, 0, w->spans.data(), w->spans.size(), &ns, &bi);
     }
     if (rc) return w->fail(HQ_E_INVAL, "hq_wire_add_batch: malformed MessageBatch");
-    w->stats.batches++;
+    hq_wire::Undo undo(*w);                          // (the stats: a batch that is not queued is
+    w->stats.batches++;                              // not counted)
     w->stats.bytes += len;
     if (bi.deployment_id != w->deployment_id || bi.bin_ver != HQ_RPC_BIN_VERSION) {
         w->stats.dropped_batches++;
         w->stats.dropped_messages += bi.n_messages;
-        return HQ_OK;
+    } else if (bi.n_messages) {
+        rc = hq_wire_dev_add_batch(w->dev, bytes, len, w->spans.data(), ns, bi.n_messages, index);
+        if (rc) return w->fail(rc, hq_wire_dev_error(w->dev));
+        w->dev_queued += bi.n_messages;
     }
-    if (bi.n_messages == 0) return HQ_OK;
-    rc = hq_wire_dev_add_batch(w->dev, bytes, len, w->spans.data(), ns, bi.n_messages, index);
-    if (rc) {
-        w->stats.batches--;
-        w->stats.bytes -= len;
-        return w->fail(rc, hq_wire_dev_error(w->dev));
-    }
-    w->dev_queued += bi.n_messages;
+    undo.keep = true;
     return HQ_OK;
 }
 
-int hq_wire_add_batch(hq_wire *w, const uint8_t *bytes, size_t len) {
-    if (!w) return HQ_E_INVAL;
+// All or nothing: after an exception the queue, the per-handle counts, the clusters seen and the
+// stats are as before the call (hq_wire::Undo; in the device mode the stats, and what
+// hq_wire_dev_add_batch leaves of a batch it could not queue is its own). Cluster ids newly cached
+// in handle_of may stay: a cache of facts that do not change.
+static int add_batch(hq_wire *w, const uint8_t *bytes, size_t len) {
     if (!bytes && len) return w->fail(HQ_E_INVAL, "hq_wire_add_batch: NULL bytes");
     if (w->dev) return add_batch_device(w, bytes, len);
-    // one pass: every message straight into a record (Message.MarshalTo's field order on the fast
-    // path, any order on the general one) with its cluster id aside; the batch's own fields
-    // (they follow the messages in the marshalled order) then decide whether the records stay
-    // and their clusters are resolved to keys
-    const size_t r0 = w->recs.size();
+    // one pass: every message straight into a record (Message.MarshalTo's field order on the
+    // fast path, any order on the general one) with its cluster id aside; the batch's own
+    // fields (they follow the messages in the marshalled order) then decide whether the
+    // records stay and their clusters are resolved to keys
+    hq_wire::Undo undo(*w);
+    const size_t r0 = undo.r0;
     w->pending.clear();
     uint64_t entries = 0, snap = 0, no_cluster = 0;
-    // attached: each record's key (the worker's handle) looked up while the batch decodes, kAhead
-    // messages behind the decode (the handle table's slot prefetched when the message is decoded;
-    // a batch the deployment check drops afterwards only leaves its clusters' handles cached);
-    // else the keys wait for that check (an index of first appearance must not see a dropped
-    // batch)
+    // attached: each record's key (the worker's handle) looked up while the batch decodes,
+    // kAhead messages behind the decode (the handle table's slot prefetched when the message is
+    // decoded; a batch the deployment check drops afterwards only leaves its clusters' handles
+    // cached); else the keys wait for that check (an index of first appearance must not see a
+    // dropped batch)
     const bool now = w->worker != nullptr;
     constexpr size_t kAhead = 8;
     size_t looked = 0;
     auto look_up = [&]() {
         Rec &x = w->recs[r0 + looked];
-        const uint64_t id = w->pending[looked++];
+        const uint64_t id = w->pending[looked];
         if (w->handle_of.find(id, &x.key) || w->key(id, &x.key)) {
             w->count_key(x.key);
         } else {
             x.key = hq_wire::kNoKey;
             ++no_cluster;
         }
+        ++looked;
     };
     hqw::error err{};
     hq_wire_batch_info bi;
@@ -491,14 +585,7 @@ int hq_wire_add_batch(hq_wire *w, const uint8_t *bytes, size_t len) {
         if (!decode_marshal_order(m, k, r, cid, ent)) {
             hq_wire_message x;
             if (!hqw::decode_message(m, k, x, err)) return HQ_E_INVAL;
-            r.kind = HQ_EV_MESSAGE;
-            r.type = x.ev.type;
-            r.from = x.ev.from;
-            r.term = x.ev.term;
-            r.log_index = x.ev.log_index;
-            r.hint = x.ev.hint;
-            r.hint_high = x.ev.hint_high;
-            r.reject = x.ev.reject != 0;
+            hqs::from_event(r, x.ev);
             cid = x.cluster_id;
             ent = x.n_entries;
         }
@@ -517,104 +604,127 @@ int hq_wire_add_batch(hq_wire *w, const uint8_t *bytes, size_t len) {
         }
         return HQ_OK;
     };
-    const int rc = hqw::walk_batch(bytes, len, bi, on_message, [] {});
-    const uint64_t n = bi.n_messages;
-    if (now) {
-        while (looked < w->pending.size()) look_up();
-        if (no_cluster && !rc) {       // the records of clusters the worker does not run leave
-            size_t o = r0;
-            for (size_t i = r0; i < w->recs.size(); ++i)
-                if (w->recs[i].key != hq_wire::kNoKey) w->recs[o++] = w->recs[i];
-            w->recs.resize(o);
-        }
+    int rc;
+    try {
+        rc = hqw::walk_batch(bytes, len, bi, on_message, [] {});
+        while (now && looked < w->pending.size()) look_up();
+    } catch (...) {                // (`looked` stays a local of the decode loop: `undo`
+        undo.counted = looked;     // learns of the keys counted only here and below)
+        throw;
     }
-    if (rc) {
-        w->drop_from(r0);
+    undo.counted = looked;
+    const uint64_t n = bi.n_messages;
+    if (no_cluster && !rc) {       // the records of clusters the worker does not run leave
+        size_t o = r0;
+        for (size_t i = r0; i < w->recs.size(); ++i)
+            if (w->recs[i].key != hq_wire::kNoKey) w->recs[o++] = w->recs[i];
+        w->recs.resize(o);
+        undo.counted = o - r0;
+    }
+    if (rc)                        // (the records leave with `undo`)
         return w->fail(HQ_E_INVAL, "hq_wire_add_batch: malformed MessageBatch" +
                                        (err.code ? ": " + message_error(err) : std::string()));
-    }
     w->stats.batches++;
     w->stats.bytes += len;
     // Transport.handleRequest (transport.go:289-300): the whole batch is dropped on a foreign
     // deployment id or binary version (none of its clusters is looked at)
     if (bi.deployment_id != w->deployment_id || bi.bin_ver != HQ_RPC_BIN_VERSION) {
-        w->drop_from(r0);
+        undo.drop();
         w->stats.dropped_batches++;
         w->stats.dropped_messages += n;
-        return HQ_OK;
+    } else {
+        w->stats.messages += n;
+        w->stats.entries += entries;
+        w->stats.snapshot_received += snap;
+        w->stats.dropped_no_cluster += no_cluster;
+        if (!now) w->resolve(r0);
     }
-    w->stats.messages += n;
-    w->stats.entries += entries;
-    w->stats.snapshot_received += snap;
-    w->stats.dropped_no_cluster += no_cluster;
-    if (!now) w->resolve(r0);
+    undo.keep = true;
     return HQ_OK;
 }
 
-int hq_wire_step_input(hq_wire *w, hq_worker *worker, hq_step_input *out, hq_wire_stats *stats) {
-    if (!w || !worker || !out) return HQ_E_INVAL;
+int hq_wire_add_batch(hq_wire *w, const uint8_t *bytes, size_t len) {
+    return guarded(w, "hq_wire_add_batch", [&] { return add_batch(w, bytes, len); });
+}
+
+// hq_wire_step_input, hq_wire_step_stream, hq_wire_step_sized: an exception leaves the queue and
+// the stats untouched; what the call had assembled is invalid until the next successful call.
+// (*dropped: the events of clusters the worker does not run, for the entry to count once nothing
+// of it can throw any more)
+static int step_input(hq_wire *w, hq_worker *worker, hq_step_input *out, uint64_t *dropped) {
+    if (!worker || !out) return HQ_E_INVAL;
     if (w->worker) return w->fail(HQ_E_STATE, "hq_wire_step_input: attached (hq_wire_step_sized)");
     const uint32_t nc = (uint32_t)w->clusters.size();
     // handles; clusters this worker does not run are dropped (nodehost.go:2045-2046)
-    std::vector<uint32_t> handle(nc);
-    std::vector<uint64_t> cnt((size_t)nc * 4 + 1, 0);
+    w->handle.resize(nc);
     for (uint32_t k = 0; k < nc; ++k)
-        if (hq_worker_find(worker, w->clusters[k], &handle[k]) != HQ_OK) handle[k] = UINT32_MAX;
+        if (hq_worker_find(worker, w->clusters[k], &w->handle[k]) != HQ_OK) w->handle[k] = UINT32_MAX;
     // counting sort by (cluster order of first appearance, category), stable in arrival order
-    for (const auto &r : w->recs) cnt[(size_t)r.key * 4 + r.cat + 1]++;
-    for (size_t i = 1; i < cnt.size(); ++i) cnt[i] += cnt[i - 1];
-    std::vector<uint32_t> perm(w->recs.size());
-    std::vector<uint64_t> pos(cnt.begin(), cnt.end() - 1);
-    for (uint32_t i = 0; i < (uint32_t)w->recs.size(); ++i) {
-        const Rec &r = w->recs[i];
-        perm[pos[(size_t)r.key * 4 + r.cat]++] = i;
-    }
+    w->cnt.assign((size_t)nc * 4 + 1, 0);
+    for (const auto &r : w->recs) w->cnt[(size_t)r.key * 4 + r.cat + 1]++;
+    w->scatter([](const Rec &r) { return (size_t)r.key * 4 + r.cat; });
     w->groups.clear();
     w->offsets.assign(1, 0);
     w->events.clear();
+    *dropped = 0;
     for (uint32_t k = 0; k < nc; ++k) {
-        const uint64_t b = cnt[(size_t)k * 4], e = cnt[(size_t)k * 4 + 4];
-        if (handle[k] == UINT32_MAX) {
-            w->stats.dropped_no_cluster += e - b;
+        const uint64_t b = w->cnt[(size_t)k * 4], e = w->cnt[(size_t)k * 4 + 4];
+        if (w->handle[k] == UINT32_MAX) {
+            *dropped += e - b;
             continue;
         }
         if (b == e) continue;
-        w->groups.push_back(handle[k]);
-        for (uint64_t j = b; j < e; ++j) w->events.push_back(hqs::to_event(w->recs[perm[j]]));
+        w->groups.push_back(w->handle[k]);
+        for (uint64_t j = b; j < e; ++j) w->events.push_back(hqs::to_event(w->recs[w->perm[j]]));
         w->offsets.push_back(w->events.size());
     }
     out->n_groups = w->groups.size();
     out->groups = w->groups.data();
     out->offsets = w->offsets.data();
     out->events = w->events.data();
-    if (stats) *stats = w->stats;
     return HQ_OK;
+}
+
+int hq_wire_step_input(hq_wire *w, hq_worker *worker, hq_step_input *out, hq_wire_stats *stats) {
+    return guarded(w, "hq_wire_step_input", [&] {
+        uint64_t dropped;
+        const int rc = step_input(w, worker, out, &dropped);
+        if (rc) return rc;
+        w->stats.dropped_no_cluster += dropped;
+        if (stats) *stats = w->stats;
+        return HQ_OK;
+    });
 }
 
 int hq_wire_step_stream(hq_wire *w, hq_worker *worker, hq_step_stream *out, hq_wire_stats *stats) {
-    if (!w || !out) return HQ_E_INVAL;
-    hq_step_input in;
-    int rc = hq_wire_step_input(w, worker, &in, stats);
-    if (rc) return rc;
-    w->boffsets.resize(in.n_groups + 1);
-    w->bytes.resize((size_t)w->events.size() * HQ_EVENT_STREAM_MAX);
-    rc = hq_events_encode(in.n_groups, in.offsets, in.events, w->bytes.data(), w->bytes.size(),
-                          w->boffsets.data());
-    if (rc) return w->fail(rc, "hq_wire_step_stream: encode");
-    out->n_groups = in.n_groups;
-    out->groups = in.groups;
-    out->offsets = in.offsets;
-    out->boffsets = w->boffsets.data();
-    out->bytes = w->bytes.data();
-    out->sizes = nullptr;
-    out->n_events = out->n_bytes = 0;
-    out->sizes16 = nullptr;
-    return HQ_OK;
+    return guarded(w, "hq_wire_step_stream", [&] {
+        if (!out) return HQ_E_INVAL;
+        hq_step_input in;
+        uint64_t dropped;
+        int rc = step_input(w, worker, &in, &dropped);
+        if (rc) return rc;
+        w->boffsets.resize(in.n_groups + 1);
+        w->bytes.resize((size_t)w->events.size() * HQ_EVENT_STREAM_MAX);
+        w->stats.dropped_no_cluster += dropped;
+        if (stats) *stats = w->stats;
+        rc = hq_events_encode(in.n_groups, in.offsets, in.events, w->bytes.data(), w->bytes.size(),
+                              w->boffsets.data());
+        if (rc) return w->fail(rc, "hq_wire_step_stream: encode");
+        out->n_groups = in.n_groups;
+        out->groups = in.groups;
+        out->offsets = in.offsets;
+        out->boffsets = w->boffsets.data();
+        out->bytes = w->bytes.data();
+        out->sizes = nullptr;
+        out->n_events = out->n_bytes = 0;
+        out->sizes16 = nullptr;
+        return HQ_OK;
+    });
 }
 
-int hq_wire_step_sized(hq_wire *w, uint8_t *bytes, uint64_t cap, uint16_t *sizes16, uint64_t n_cap,
-                       hq_step_stream *out, hq_wire_stats *stats) {
-    if (!w || !out || (cap && !bytes)) return HQ_E_INVAL;
+static int step_sized(hq_wire *w, uint8_t *bytes, uint64_t cap, uint16_t *sizes16, uint64_t n_cap,
+                      hq_step_stream *out, hq_wire_stats *stats) {
+    if (!out || (cap && !bytes)) return HQ_E_INVAL;
     if (!w->worker) return w->fail(HQ_E_STATE, "hq_wire_step_sized: no worker attached");
     if (w->dev) return w->fail(HQ_E_STATE, "hq_wire_step_sized: device mode (hq_wire_step_device)");
     uint64_t n = 0;
@@ -624,16 +734,12 @@ int hq_wire_step_sized(hq_wire *w, uint8_t *bytes, uint64_t cap, uint16_t *sizes
     // counting sort of the records by handle, stable in arrival order; each handle's records
     // then taken category by category (node.handleEvents: local ReadIndex, received messages,
     // ticks, proposals)
-    const uint32_t nr = (uint32_t)w->recs.size();
     // (the counts per handle were kept as the records were queued; handles only grow, so every
     // queued key is below n)
     w->cnt.assign(n + 1, 0);
     std::copy(w->kcnt.begin(), w->kcnt.begin() + std::min<size_t>(w->kcnt.size(), n + 1), w->cnt.begin());
-    for (uint64_t h = 0; h < n; ++h) w->cnt[h + 1] += w->cnt[h];
-    if (w->cnt[n] != nr) return w->fail(HQ_E_STATE, "hq_wire_step_sized: a queued record's handle is past the worker's groups");
-    w->perm.resize(nr);
-    w->pos.assign(w->cnt.begin(), w->cnt.end() - 1);
-    for (uint32_t i = 0; i < nr; ++i) w->perm[w->pos[w->recs[i].key]++] = i;
+    if (!w->scatter([](const Rec &r) { return r.key; }))
+        return w->fail(HQ_E_STATE, "hq_wire_step_sized: a queued record's handle is past the worker's groups");
     uint8_t *p = bytes, *const end = bytes + cap;
     uint64_t events = 0;
     for (uint64_t h = 0; h < n; ++h) {
@@ -670,56 +776,69 @@ int hq_wire_step_sized(hq_wire *w, uint8_t *bytes, uint64_t cap, uint16_t *sizes
     return HQ_OK;
 }
 
+int hq_wire_step_sized(hq_wire *w, uint8_t *bytes, uint64_t cap, uint16_t *sizes16, uint64_t n_cap,
+                       hq_step_stream *out, hq_wire_stats *stats) {
+    return guarded(w, "hq_wire_step_sized", [&] { return step_sized(w, bytes, cap, sizes16, n_cap, out, stats); });
+}
+
+// What a failed device step leaves in the worker and in the device queue is unspecified, as
+// after any failed step; the wire itself is usable again after hq_wire_reset.
 int hq_wire_step_device(hq_wire *w, hq_step_output *out, hq_wire_stats *stats) {
-    if (!w || !out) return HQ_E_INVAL;
-    if (!w->dev) return w->fail(HQ_E_STATE, "hq_wire_step_device: no device worker attached");
-    uint64_t c[4], rejected_bytes = 0, n_bad_message = 0;
-    hq_wire_stats add{};
-    const int rc = hq_wire_dev_step(w->dev, static_cast<const hqs::WireEvent *>(w->recs.data()),
-                                    w->recs.size(), out, c, &w->rejected, &w->n_rejected,
-                                    &rejected_bytes, &n_bad_message, &add);
-    if (rc) return w->fail(rc, hq_wire_dev_error(w->dev));
-    if (stats) {
-        // the kernels' counters beside the host's (with the framing on the device, the batches'
-        // own counts come from its results); a batch dropped for a malformed message is counted
-        // nowhere (as one hq_wire_add_batch rejects)
-        *stats = w->stats;
-        stats->batches += add.batches;
-        stats->bytes += add.bytes;
-        stats->dropped_batches += add.dropped_batches;
-        stats->dropped_messages += add.dropped_messages;
-        stats->messages += c[0];
-        stats->entries += c[1];
-        stats->snapshot_received += c[2];
-        stats->dropped_no_cluster += c[3];
-        stats->batches -= n_bad_message;
-        stats->bytes -= rejected_bytes;
-    }
-    return HQ_OK;
+    return guarded(w, "hq_wire_step_device", [&] {
+        if (!out) return HQ_E_INVAL;
+        if (!w->dev) return w->fail(HQ_E_STATE, "hq_wire_step_device: no device worker attached");
+        uint64_t c[4], rejected_bytes = 0, n_bad_message = 0;
+        hq_wire_stats add{};
+        const int rc = hq_wire_dev_step(w->dev, static_cast<const hqs::WireEvent *>(w->recs.data()),
+                                        w->recs.size(), out, c, &w->rejected, &w->n_rejected,
+                                        &rejected_bytes, &n_bad_message, &add);
+        if (rc) return w->fail(rc, hq_wire_dev_error(w->dev));
+        if (stats) {
+            // the kernels' counters beside the host's (with the framing on the device, the
+            // batches' own counts come from its results); a batch dropped for a malformed message
+            // is counted nowhere (as one hq_wire_add_batch rejects)
+            *stats = w->stats;
+            stats->batches += add.batches;
+            stats->bytes += add.bytes;
+            stats->dropped_batches += add.dropped_batches;
+            stats->dropped_messages += add.dropped_messages;
+            stats->messages += c[0];
+            stats->entries += c[1];
+            stats->snapshot_received += c[2];
+            stats->dropped_no_cluster += c[3];
+            stats->batches -= n_bad_message;
+            stats->bytes -= rejected_bytes;
+        }
+        return HQ_OK;
+    });
 }
 
 int hq_wire_set_device_framing(hq_wire *w, int on) {
-    if (!w) return HQ_E_INVAL;
-    if (!w->dev) return w->fail(HQ_E_STATE, "hq_wire_set_device_framing: no device worker attached");
-    if (!w->recs.empty() || w->dev_queued)
-        return w->fail(HQ_E_STATE, "hq_wire_set_device_framing: events queued (reset first)");
-    hq_wire_dev_set_framing(w->dev, on != 0, w->deployment_id);
-    return HQ_OK;
+    return guarded(w, "hq_wire_set_device_framing", [&] {
+        if (!w->dev) return w->fail(HQ_E_STATE, "hq_wire_set_device_framing: no device worker attached");
+        if (const int rc = w->need_empty("hq_wire_set_device_framing")) return rc;
+        hq_wire_dev_set_framing(w->dev, on != 0, w->deployment_id);
+        return HQ_OK;
+    });
 }
 
 int hq_wire_device_frame_stats(hq_wire *w, uint64_t out[4]) {
-    if (!w || !out) return HQ_E_INVAL;
-    if (!w->dev) return w->fail(HQ_E_STATE, "hq_wire_device_frame_stats: no device worker attached");
-    hq_wire_dev_frame_stats(w->dev, out);
-    return HQ_OK;
+    return guarded(w, "hq_wire_device_frame_stats", [&] {
+        if (!out) return HQ_E_INVAL;
+        if (!w->dev) return w->fail(HQ_E_STATE, "hq_wire_device_frame_stats: no device worker attached");
+        hq_wire_dev_frame_stats(w->dev, out);
+        return HQ_OK;
+    });
 }
 
 int hq_wire_device_rejected(hq_wire *w, const uint32_t **batches, uint64_t *n) {
-    if (!w || !batches || !n) return HQ_E_INVAL;
-    if (!w->dev) return w->fail(HQ_E_STATE, "hq_wire_device_rejected: no device worker attached");
-    *batches = w->rejected;
-    *n = w->n_rejected;
-    return HQ_OK;
+    return guarded(w, "hq_wire_device_rejected", [&] {
+        if (!batches || !n) return HQ_E_INVAL;
+        if (!w->dev) return w->fail(HQ_E_STATE, "hq_wire_device_rejected: no device worker attached");
+        *batches = w->rejected;
+        *n = w->n_rejected;
+        return HQ_OK;
+    });
 }
 
 }  // extern "C"

@@ -296,7 +296,7 @@ int hq_heartbeats_expand(const hq_heartbeat_output *hb, const uint64_t *cluster_
                          const uint64_t *member_ids, hq_heartbeat_msg *msgs, uint64_t cap,
                          uint64_t *n) {
     // (no worker: nowhere to keep a message)
-    return hq::guard("hq_heartbeats_expand", [](int, const std::string &) {}, [&] {
+    return hq::guard("hq_heartbeats_expand", [&] {
         return heartbeats_expand(hb, cluster_id, term, committed, n_members, member_ids, msgs, cap, n);
     });
 }

@@ -47,9 +47,13 @@ int hq_wire_dev_add_batch(hq_wire_dev *, const uint8_t *, size_t, const hq_wire_
     return HQ_E_DEVICE;
 }
 int hq_wire_dev_step(hq_wire_dev *, const hqs::WireEvent *, uint64_t, hq_step_output *, uint64_t[4],
-                     const uint32_t **, uint64_t *, uint64_t *) {
+                     const uint32_t **, uint64_t *, uint64_t *, uint64_t *, hq_wire_stats *) {
     return HQ_E_DEVICE;
 }
+void hq_wire_dev_set_framing(hq_wire_dev *, bool, uint64_t) {}
+bool hq_wire_dev_framing(const hq_wire_dev *) { return false; }
+int hq_wire_dev_queue(hq_wire_dev *, const uint8_t *, size_t, uint32_t) { return HQ_E_DEVICE; }
+void hq_wire_dev_frame_stats(const hq_wire_dev *, uint64_t[4]) {}
 
 static double now_s() {
     return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
