@@ -642,7 +642,7 @@ int launch_bits(hq_ctx *ctx, BitsK &k, const char *what) {
     const uint64_t slots = k.n16 > k.n16o ? k.n16 : k.n16o;
     int rc = hq::pre_launch(ctx);
     if (rc) return rc;
-    const dim3 grid(grid_for(slots)), block(kBlock);
+    const dim3 grid(grid_for(ctx, slots)), block(kBlock);
     if (k.tiles) {
         // tiles exist for the fused ReadIndex + vote pass only; rows [n] ack granted rejected
         if constexpr (MODE == (kRI | kVOTE))
@@ -742,7 +742,7 @@ extern "C" int hq_readindex_vote_tiles3_dev(hq_ctx *ctx, uint64_t G, const uint8
     int rc = hq::pre_launch(ctx);
     if (rc) return rc;
     const uint64_t ntiles = (G + 1023) / 1024;
-    hipLaunchKernelGGL(k_bits3<256>, dim3(grid_for((ntiles + kB3TPW - 1) / kB3TPW * 64, 256)),
+    hipLaunchKernelGGL(k_bits3<256>, dim3(grid_for(ctx, (ntiles + kB3TPW - 1) / kB3TPW * 64, 256)),
                        dim3(256), 0, ctx->stream, k);
     return hq::post_launch(ctx, "hq_readindex_vote_tiles3");
 }
@@ -762,7 +762,7 @@ extern "C" int hq_readindex_vote_planes_dev(hq_ctx *ctx, uint64_t G, const uint8
     if (rc) return rc;
     const uint64_t ntiles = (G + kPlaneTile - 1) / kPlaneTile;
     hipLaunchKernelGGL(k_planes<kPlBlock>,
-                       dim3(grid_for((ntiles + kPlTPW - 1) / kPlTPW * 64, kPlBlock)),
+                       dim3(grid_for(ctx, (ntiles + kPlTPW - 1) / kPlTPW * 64, kPlBlock)),
                        dim3(kPlBlock), 0, ctx->stream, k);
     return hq::post_launch(ctx, "hq_readindex_vote_planes");
 }
@@ -785,7 +785,7 @@ extern "C" int hq_readindex_vote_cq_planes_dev(hq_ctx *ctx, uint64_t G, const ui
     if (rc) return rc;
     const uint64_t ntiles = (G + kPlaneTile - 1) / kPlaneTile;
     hipLaunchKernelGGL(k_planes_cq<kPlBlock>,
-                       dim3(grid_for((ntiles + kPlCqTPW - 1) / kPlCqTPW * 64, kPlBlock)),
+                       dim3(grid_for(ctx, (ntiles + kPlCqTPW - 1) / kPlCqTPW * 64, kPlBlock)),
                        dim3(kPlBlock), 0, ctx->stream, k, active_planes);
     return hq::post_launch(ctx, "hq_readindex_vote_cq_planes");
 }
@@ -800,7 +800,7 @@ extern "C" int hq_tile_planes_dev(hq_ctx *ctx, uint64_t G, const uint8_t *ack,
         return hq::fail(ctx, HQ_E_INVAL, "hq_tile_planes: NULL argument or planes misaligned");
     int rc = hq::pre_launch(ctx);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_tile_planes, dim3(grid_for((G + kPlaneTile - 1) / kPlaneTile * kPlaneTile)),
+    hipLaunchKernelGGL(k_tile_planes, dim3(grid_for(ctx, (G + kPlaneTile - 1) / kPlaneTile * kPlaneTile)),
                        dim3(kBlock), 0, ctx->stream, G, n_voting, n_uniform, ack, granted,
                        rejected, planes, fallback);
     return hq::post_launch(ctx, "k_tile_planes");
@@ -816,7 +816,7 @@ extern "C" int hq_tile_bits3_dev(hq_ctx *ctx, uint64_t G, const uint8_t *ack,
         return hq::fail(ctx, HQ_E_INVAL, "hq_tile_bits3: NULL argument");
     int rc = hq::pre_launch(ctx);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_tile_bits3, dim3(grid_for((G + 1023) / 1024 * 1024)), dim3(kBlock), 0,
+    hipLaunchKernelGGL(k_tile_bits3, dim3(grid_for(ctx, (G + 1023) / 1024 * 1024)), dim3(kBlock), 0,
                        ctx->stream, G, n_voting, n_uniform, ack, granted, rejected, tiles,
                        fallback);
     return hq::post_launch(ctx, "k_tile_bits3");
@@ -853,7 +853,7 @@ extern "C" int hq_tile_bits_dev(hq_ctx *ctx, uint64_t G, const uint8_t *ack,
         return hq::fail(ctx, HQ_E_INVAL, "hq_tile_bits_dev: NULL or misaligned argument");
     int rc = hq::pre_launch(ctx);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_tile_bits, dim3(grid_for(hq_bits_tiles(G) * (HQ_BITS_TILE_GROUPS / 16))),
+    hipLaunchKernelGGL(k_tile_bits, dim3(grid_for(ctx, hq_bits_tiles(G) * (HQ_BITS_TILE_GROUPS / 16))),
                        dim3(kBlock), 0, ctx->stream, G, n_voting, ack, granted, rejected, tiles,
                        n_voting ? 4u : 3u);
     return hq::post_launch(ctx, "k_tile_bits");
@@ -885,7 +885,7 @@ extern "C" int hq_check_quorum_planes_dev(hq_ctx *ctx, uint64_t G, uint8_t *plan
     int rc = hq::pre_launch(ctx);
     if (rc) return rc;
     constexpr int B = kPlBlock;
-    const dim3 grid(grid_for((G + kPlaneTile - 1) / kPlaneTile * 64, B));
+    const dim3 grid(grid_for(ctx, (G + kPlaneTile - 1) / kPlaneTile * 64, B));
     // n_uniform 0: per-group n (its planes in the tile); else n - 1 active planes
     dispatch<0, 1, 2, 3, 4, 5, 6, 7, 8>(n_uniform, [&](auto nu) {
         constexpr int n = decltype(nu)::value;
@@ -911,7 +911,7 @@ extern "C" int hq_tile_cq_planes_dev(hq_ctx *ctx, uint64_t G, const uint8_t *act
     int rc = hq::pre_launch(ctx);
     if (rc) return rc;
     hipLaunchKernelGGL(k_tile_cq_planes,
-                       dim3(grid_for((G + kPlaneTile - 1) / kPlaneTile * kPlaneTile)),
+                       dim3(grid_for(ctx, (G + kPlaneTile - 1) / kPlaneTile * kPlaneTile)),
                        dim3(kBlock), 0, ctx->stream, G, active, n_voting, n_uniform, self_slot,
                        planes, fallback);
     return hq::post_launch(ctx, "k_tile_cq_planes");

@@ -158,7 +158,7 @@ __global__ __launch_bounds__(kCommitBlockBig, 8) void k_commit_big(const CommitK
 template <int N, int FORM, int VEC, bool PERN, int TILED = 0>
 int launch_commit_t(hq_ctx *ctx, const CommitK &k) {
     constexpr int B = commit_blk<N, FORM, PERN>();
-    const unsigned grid = grid_for((k.G + VEC - 1) / VEC, B, kMaxBlocks * 256 / B);
+    const unsigned grid = grid_for_commit(ctx, (k.G + VEC - 1) / VEC, B);
     int rc = hq::pre_launch(ctx);
     if (rc) return rc;
     if constexpr (B == kCommitBlock)

@@ -264,7 +264,7 @@ __global__ __launch_bounds__(BLK, BLK > kCommitBlock ? 8 : 1) void k_commit_lag_
 template <int N, int FORM, int VEC, bool PERN, int LEAD>
 int launch_lag_t(hq_ctx *ctx, const LagK &k) {
     constexpr int B = lag_blk<N, PERN>();
-    const unsigned grid = grid_for((k.G + VEC - 1) / VEC, B, kMaxBlocks * 256 / B);
+    const unsigned grid = grid_for_commit(ctx, (k.G + VEC - 1) / VEC, B);
     int rc = hq::pre_launch(ctx);
     if (rc) return rc;
     if constexpr (B == kCommitBlock)
@@ -388,7 +388,7 @@ extern "C" int hq_commit_lag_fused_dev(hq_ctx *ctx, const hq_commit_lag_args *ar
         f.b[i] = lag_k(b);
         f.n[i] = b->n_max;
         f.first[i] = (uint32_t)blocks;
-        blocks += grid_for((b->G + kLagVec - 1) / kLagVec, B, (uint64_t)kMaxBlocks * 256 / B);
+        blocks += grid_for_commit(ctx, (b->G + kLagVec - 1) / kLagVec, B);
     }
     for (uint32_t i = count; i <= (uint32_t)kMaxFused; ++i) f.first[i] = (uint32_t)blocks;
     int rc = hq::pre_launch(ctx);

@@ -147,7 +147,7 @@ extern "C" int hq_commit_fused_dev(hq_ctx *ctx, const hq_commit_args *args, uint
         f.n[i] = args[order[k]].n_max;
         f.first[i] = (uint32_t)blocks;
         // the same lanes per batch as its own launch would get (grid-stride beyond that)
-        blocks += grid_for((args[order[k]].G + 1) / 2, B, (uint64_t)kMaxBlocks * 256 / B);
+        blocks += grid_for_commit(ctx, (args[order[k]].G + 1) / 2, B);
     }
     for (uint32_t i = count; i <= (uint32_t)kMaxFusedCommit; ++i) f.first[i] = (uint32_t)blocks;
     int rc = hq::pre_launch(ctx);
@@ -229,7 +229,7 @@ extern "C" int hq_tile_commit_as_dev(hq_ctx *ctx, const hq_commit_args *a, uint6
     const uint64_t ntiles = hq_commit_tiles(a->G);
     rc = hq::pre_launch(ctx);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_tile_commit, dim3(grid_for(ntiles * k.tile_words)), dim3(kBlock), 0,
+    hipLaunchKernelGGL(k_tile_commit, dim3(grid_for(ctx, ntiles * k.tile_words)), dim3(kBlock), 0,
                        ctx->stream, k, tiles, ntiles, a->n_max - lead, (int)a->form, lead);
     return hq::post_launch(ctx, "k_tile_commit");
 }

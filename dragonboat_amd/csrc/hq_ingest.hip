@@ -172,7 +172,7 @@ extern "C" int hq_ingest_lag_dev(hq_ctx *ctx, const uint64_t *updates, uint64_t 
         return hq::fail(ctx, HQ_E_INVAL, "hq_ingest_lag_dev: bad arguments");
     int rc = hq::pre_launch(ctx);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_ingest_lag, dim3(grid_for(count)), dim3(kBlock), 0, ctx->stream,
+    hipLaunchKernelGGL(k_ingest_lag, dim3(grid_for(ctx, count)), dim3(kBlock), 0, ctx->stream,
                        updates, count, match, match_stride, last_index, G, n_max, n_skipped);
     return hq::post_launch(ctx, "k_ingest_lag");
 }
@@ -189,7 +189,7 @@ extern "C" int hq_append_count_dev(hq_ctx *ctx, const uint64_t *updates, uint64_
         return hq::fail(ctx, HQ_E_INVAL, "hq_append_count_dev: bad arguments");
     int rc = hq::pre_launch(ctx);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_append_count, dim3(grid_for(count)), dim3(kBlock), 0, ctx->stream,
+    hipLaunchKernelGGL(k_append_count, dim3(grid_for(ctx, count)), dim3(kBlock), 0, ctx->stream,
                        updates, count, last_index, match_slot0, term_mask,
                        ring_len ? ring_len : 16u, G, n_skipped);
     return hq::post_launch(ctx, "k_append_count");
@@ -204,7 +204,7 @@ extern "C" int hq_ingest_match_dev(hq_ctx *ctx, const hq_match_update *updates, 
         return hq::fail(ctx, HQ_E_INVAL, "hq_ingest_match_dev: bad arguments");
     int rc = hq::pre_launch(ctx);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_ingest_match, dim3(grid_for(count)), dim3(kBlock), 0, ctx->stream,
+    hipLaunchKernelGGL(k_ingest_match, dim3(grid_for(ctx, count)), dim3(kBlock), 0, ctx->stream,
                        updates, count, match, match_stride, G, n_max, n_skipped);
     return hq::post_launch(ctx, "k_ingest_match");
 }
@@ -218,7 +218,7 @@ extern "C" int hq_ingest_ack_dev(hq_ctx *ctx, const uint64_t *group_slot, uint64
         return hq::fail(ctx, HQ_E_INVAL, "hq_ingest_ack_dev: bad arguments (ack must be 4-byte aligned)");
     int rc = hq::pre_launch(ctx);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_ingest_ack, dim3(grid_for(count)), dim3(kBlock), 0, ctx->stream,
+    hipLaunchKernelGGL(k_ingest_ack, dim3(grid_for(ctx, count)), dim3(kBlock), 0, ctx->stream,
                        group_slot, count, ack, G, n_max, n_skipped);
     return hq::post_launch(ctx, "k_ingest_ack");
 }
@@ -234,7 +234,7 @@ extern "C" int hq_append_dev(hq_ctx *ctx, const hq_append_update *updates, uint6
         return hq::fail(ctx, HQ_E_INVAL, "hq_append_dev: bad arguments");
     int rc = hq::pre_launch(ctx);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_append, dim3(grid_for(count)), dim3(kBlock), 0, ctx->stream, updates,
+    hipLaunchKernelGGL(k_append, dim3(grid_for(ctx, count)), dim3(kBlock), 0, ctx->stream, updates,
                        count, last_index, match_slot0, term_mask, ring_len ? ring_len : 16u, G,
                        n_skipped);
     return hq::post_launch(ctx, "k_append");

@@ -9,6 +9,10 @@
 
 #include "../../include/hipquorum.h"
 
+namespace hq {
+constexpr uint32_t kDefaultMaxBlocks = 256 * 64;   // kMaxBlocks (hq_launch.h)
+}
+
 struct hq_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -29,6 +33,9 @@ struct hq_ctx {
     // uniform multi-ctx tiles (K_max in {2, 4, 8}, n = n_max) on k_ri_tiles_u (HQ_RI_UNIFORM=0:
     // on the general k_ri_multi2, A/B)
     bool ri_uniform = true;
+    // grid cap of the grid-stride launchers, in 256-thread blocks (HQ_MAX_BLOCKS=4..kMaxBlocks at
+    // hq_open: tests lower it so that small batches make several passes)
+    uint32_t max_blocks = hq::kDefaultMaxBlocks;
     // hq_wait_for: recorded on this context's stream when another context orders after it
     hipEvent_t ev_order = nullptr;
     // device workspace for the host-pointer entry points

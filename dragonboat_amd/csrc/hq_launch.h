@@ -24,12 +24,22 @@ constexpr int kCommitBlockBig = 1024;
 // (profiles/r01e/ab_maxblocks.log).
 constexpr int kMaxBlocks = 256 * 64;
 
-inline unsigned grid_for(uint64_t lanes_needed, int block = kBlock,
-                         uint64_t max_blocks = kMaxBlocks) {
+static_assert(hq::kDefaultMaxBlocks == kMaxBlocks, "hq_ctx::max_blocks starts at the grid cap");
+
+// The cap is the context's (hq_ctx::max_blocks: kMaxBlocks unless HQ_MAX_BLOCKS lowered it at
+// hq_open, so that a test's small batch makes several grid-stride passes).
+inline unsigned grid_capped(uint64_t lanes_needed, int block, uint64_t max_blocks) {
     uint64_t b = (lanes_needed + block - 1) / block;
     if (b < 1) b = 1;
     if (b > max_blocks) b = max_blocks;
     return (unsigned)b;
+}
+inline unsigned grid_for(const hq_ctx *ctx, uint64_t lanes_needed, int block = kBlock) {
+    return grid_capped(lanes_needed, block, ctx->max_blocks);
+}
+// the commit streams: the same threads under the cap whatever the block size B
+inline unsigned grid_for_commit(const hq_ctx *ctx, uint64_t lanes_needed, int B) {
+    return grid_capped(lanes_needed, B, (uint64_t)ctx->max_blocks * 256 / B);
 }
 
 // A run-time value from the fixed list Vs as a compile-time constant: calls f with the

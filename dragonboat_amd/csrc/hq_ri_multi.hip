@@ -417,7 +417,7 @@ extern "C" int hq_readindex_multi_dev(hq_ctx *ctx, uint64_t G, uint32_t K_max, u
     const bool pairs = ctx->ri_pairs && G % 2 == 0 && al(ack_ordinal, 4) && al(ctx_index, 16) &&
                        al(released_index, 16) && al(released_count, 2) && al(batch_end, 2) &&
                        al(n_pending, 2) && al(n_voting, 2);
-    const unsigned grid = pairs ? grid_for(G / 2) : grid_for(G);
+    const unsigned grid = pairs ? grid_for(ctx, G / 2) : grid_for(ctx, G);
     int rc = hq::pre_launch(ctx);
     if (rc) return rc;
     const int km = K_max <= 2 ? 2 : K_max <= 4 ? 4 : 8;   // ctx slots the pair kernel holds
@@ -511,7 +511,7 @@ extern "C" int hq_readindex_multi_tiles_dev(hq_ctx *ctx, uint64_t G, uint32_t K_
     // the pair kernel's column stores need 16-byte rows: G even keeps k * G + g aligned
     if (G % 2)
         return hq::fail(ctx, HQ_E_INVAL, "hq_readindex_multi_tiles_dev: G must be even");
-    const unsigned grid = grid_for(G / 2);
+    const unsigned grid = grid_for(ctx, G / 2);
     int rc = hq::pre_launch(ctx);
     if (rc) return rc;
     const int km = K_max <= 2 ? 2 : K_max <= 4 ? 4 : 8;
@@ -554,7 +554,7 @@ extern "C" int hq_tile_ri_multi_dev(hq_ctx *ctx, uint64_t G, uint32_t K_max, uin
     const uint64_t ntiles = (G + HQ_RI_TILE_GROUPS - 1) / HQ_RI_TILE_GROUPS;
     int rc = hq::pre_launch(ctx);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_tile_ri_multi, dim3(grid_for(ntiles * (tb / 16))), dim3(kBlock), 0,
+    hipLaunchKernelGGL(k_tile_ri_multi, dim3(grid_for(ctx, ntiles * (tb / 16))), dim3(kBlock), 0,
                        ctx->stream, G, K_max, n_max, ack_ordinal, ctx_index, n_pending, n_voting,
                        tiles, tb);
     return hq::post_launch(ctx, "k_tile_ri_multi");

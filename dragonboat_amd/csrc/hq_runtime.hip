@@ -128,6 +128,11 @@ int hq_open(int device, uint32_t flags, hq_ctx **out) {
     ctx->device = device;
     if (const char *r = std::getenv("HQ_RI_PAIRS")) ctx->ri_pairs = std::atoi(r) != 0;
     if (const char *r = std::getenv("HQ_RI_UNIFORM")) ctx->ri_uniform = std::atoi(r) != 0;
+    if (const char *mb = std::getenv("HQ_MAX_BLOCKS")) {
+        const int v = std::atoi(mb);
+        // >= 4: the commit launchers scale the cap by 256 / B with B up to 1024
+        if (v >= 4 && v <= (int)hq::kDefaultMaxBlocks) ctx->max_blocks = (uint32_t)v;
+    }
     if (const char *gd = std::getenv("HQ_BIN_GRID")) {
         const int v = std::atoi(gd);
         if (v >= 8 && v <= 4096) ctx->bin_grid = (uint32_t)(v & ~7);

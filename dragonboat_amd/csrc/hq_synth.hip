@@ -177,7 +177,7 @@ extern "C" int hq_synth_commit_dev(hq_ctx *ctx, const hq_synth_spec *s,
         return hq::fail(ctx, HQ_E_INVAL, "hq_synth_commit: term_mask needs ring_len <= 16");
     int rc = hq::pre_launch(ctx);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_synth_commit, dim3(grid_for(s->G)), dim3(kBlock), 0, ctx->stream, *s, o,
+    hipLaunchKernelGGL(k_synth_commit, dim3(grid_for(ctx, s->G)), dim3(kBlock), 0, ctx->stream, *s, o,
                        LagOut{});
     return hq::post_launch(ctx, "k_synth_commit");
 }
@@ -200,7 +200,7 @@ extern "C" int hq_synth_commit_lag_dev(hq_ctx *ctx, const hq_synth_spec *s,
               const_cast<int32_t *>(a->ts_lag), const_cast<uint16_t *>(a->lag_mask), last_index};
     int rc = hq::pre_launch(ctx);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_synth_commit, dim3(grid_for(s->G)), dim3(kBlock), 0, ctx->stream, *s, o,
+    hipLaunchKernelGGL(k_synth_commit, dim3(grid_for(ctx, s->G)), dim3(kBlock), 0, ctx->stream, *s, o,
                        lo);
     return hq::post_launch(ctx, "k_synth_commit");
 }
@@ -213,7 +213,7 @@ extern "C" int hq_synth_bitmaps_dev(hq_ctx *ctx, const hq_synth_spec *s, uint8_t
     if (s->G == 0) return HQ_OK;
     int rc = hq::pre_launch(ctx);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_synth_bits, dim3(grid_for(s->G)), dim3(kBlock), 0, ctx->stream, *s, ack,
+    hipLaunchKernelGGL(k_synth_bits, dim3(grid_for(ctx, s->G)), dim3(kBlock), 0, ctx->stream, *s, ack,
                        granted, rejected, n_voting);
     return hq::post_launch(ctx, "k_synth_bits");
 }
