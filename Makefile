@@ -9,7 +9,7 @@ SRCS := $(CSRC)/hq_runtime.hip $(CSRC)/hq_commit.hip $(CSRC)/hq_commit_tiles.hip
         $(CSRC)/hq_commit_lag.hip $(CSRC)/hq_bits.hip $(CSRC)/hq_ri_multi.hip $(CSRC)/hq_synth.hip \
         $(CSRC)/hq_ingest.hip $(CSRC)/hq_table.hip $(CSRC)/hq_pack.cpp $(CSRC)/hq_worker.cpp \
         $(CSRC)/hq_worker_host.cpp $(CSRC)/hq_worker_dev.cpp $(CSRC)/hq_worker_hb.cpp \
-        $(CSRC)/hq_worker_lists.cpp \
+        $(CSRC)/hq_worker_lists.cpp $(CSRC)/hq_worker_lifecycle.cpp $(CSRC)/hq_pool.hip \
         $(CSRC)/hq_wire.cpp $(CSRC)/hq_stream.cpp $(CSRC)/hq_stream16.cpp $(CSRC)/hq_jobs.cpp $(CSRC)/hq_dstep.hip \
         $(CSRC)/hq_dstep_step.hip $(CSRC)/hq_dstep_layout.hip $(CSRC)/hq_dstep_run.hip \
         $(CSRC)/hq_engine.hip $(CSRC)/hq_wire_frame.cpp $(CSRC)/hq_wire_dev.hip \

@@ -125,6 +125,17 @@ void hq_dstep_view_mut(hq_dstep *d, hq_dstate_mut *out);
 // member records [m0, total) reserved at the pool's end, zeroed (the member arrays grown to hold
 // `total` records; the records below m0 keep their contents)
 int hq_dstep_reserve_members(hq_dstep *d, uint64_t m0, uint64_t total);
+// group records [n_groups, total) reserved at the arrays' end for a kernel to write (hq_groups.hip,
+// hq_worker_start_groups): the group-side twin of hq_dstep_reserve_members. The group, read and
+// stamp arrays are grown to hold `total` records with their contents kept, the saved-state arrays
+// without (as hq_dstep_put grows them); the new stamps are zeroed and n_groups is raised.
+int hq_dstep_reserve_groups(hq_dstep *d, uint64_t total);
+// hq_worker_compact (hq_pool.hip): a second member pool of the current one's capacity for a kernel
+// to fill, then either installed in the current one's place (which is freed; the stream must be
+// idle) or dropped. The saved matches are sized by the capacity and need no contents.
+int hq_dstep_members_spare(hq_dstep *d, hq_dmember **spare, uint64_t *capacity);
+void hq_dstep_members_install(hq_dstep *d, hq_dmember *spare);
+void hq_dstep_members_drop(hq_dstep *d, hq_dmember *spare);
 // a group edited on the device may now have n members: the step's kernels are chosen by the most
 // members of any group (8 member slots in registers, or kDMembers)
 void hq_dstep_raise_max_members(hq_dstep *d, uint32_t n);
@@ -148,6 +159,11 @@ int hq_worker_step_jobs_fused(hq_step_job *jobs, uint32_t count);
 // whatever produced them)
 hq_ctx *hq_worker_device_ctx(hq_worker *w);
 int hq_worker_cluster_ids(hq_worker *w, uint64_t h0, uint64_t n, uint64_t *out);
+// hq_worker_lifecycle.cpp, for both attached wire modes (hq_wire.cpp, hq_wire_dev.hip): the
+// worker's lifecycle epoch (hq_worker_pool_info's: it moves when handles have changed their
+// clusters) and which of handles [h0, h0 + n) are live (1) or vacant (0)
+uint64_t hq_worker_epoch(hq_worker *w);
+int hq_worker_live_handles(hq_worker *w, uint64_t h0, uint64_t n, uint8_t *out);
 int hq_worker_step_device_rows(hq_worker *w, uint64_t n, const uint32_t *groups,
                                const uint64_t *offsets, const hq_event *events, uint64_t n_events,
                                hq_step_output *out);

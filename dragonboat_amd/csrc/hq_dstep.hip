@@ -193,6 +193,30 @@ int wait_stream(hq_dstep *d, hipStream_t s, const char *what) {
 
 }  // namespace hq
 
+namespace {
+
+// The per-group arrays grown to hold `need` records: groups, reads and stamps with their contents,
+// the saved-state buffers (they only live within a step) without.
+int grow_groups(hq_dstep *d, uint64_t need) {
+    if (need <= d->gcap) return HQ_OK;
+    hq_ctx *ctx = d->ctx;
+    size_t gc = d->gcap * sizeof(hq_dgroup), rcap = d->gcap * kDReads * sizeof(hq_dread);
+    int rc = grow(ctx, &d->groups, &gc, need * sizeof(hq_dgroup), true, "hq_dstep groups");
+    if (!rc) rc = grow(ctx, &d->reads, &rcap, need * kDReads * sizeof(hq_dread), true, "hq_dstep reads");
+    size_t sc = d->gcap * 4;
+    if (!rc) rc = grow(ctx, &d->stamp, &sc, need * 4, true, "hq_dstep stamps");
+    size_t gn = d->gcap * sizeof(hq_dgroup), rn = d->gcap * kDReads * sizeof(hq_dread);
+    if (!rc) rc = grow(ctx, &d->groups_old, &gn, need * sizeof(hq_dgroup), false, "hq_dstep saved groups");
+    if (!rc)
+        rc = grow(ctx, &d->reads_old, &rn, need * kDReads * sizeof(hq_dread), false, "hq_dstep saved reads");
+    if (!rc) d->gcap = std::min({gc / sizeof(hq_dgroup), rcap / (kDReads * sizeof(hq_dread)),
+                                 sc / 4, gn / sizeof(hq_dgroup),
+                                 rn / (kDReads * sizeof(hq_dread))});
+    return rc;
+}
+
+}  // namespace
+
 int hq_dstep_set_wait(hq_dstep *d, uint32_t mode, uint32_t poll_us, uint32_t sleep_us) {
     const uint32_t m = mode & ~HQ_WAIT_CLOCK;
     if (m != HQ_WAIT_BLOCK && m != HQ_WAIT_SLEEP && m != HQ_WAIT_SPIN && m != HQ_WAIT_ADAPT)
@@ -281,27 +305,8 @@ int hq_dstep_put(hq_dstep *d, uint64_t g0, uint64_t ng, const hq_dgroup *g, cons
                  uint64_t m0, uint64_t nm, const hq_dmember *m) {
     hq_ctx *ctx = d->ctx;
     int rc = hq::check_hip(ctx, hipSetDevice(ctx->device), "hipSetDevice");
-    size_t gc = d->gcap * sizeof(hq_dgroup), rcap = d->gcap * kDReads * sizeof(hq_dread),
-           mc = d->mcap * sizeof(hq_dmember);
-    if (!rc && (g0 + ng) > d->gcap) {
-        rc = grow(ctx, &d->groups, &gc, (g0 + ng) * sizeof(hq_dgroup), true, "hq_dstep groups");
-        if (!rc)
-            rc = grow(ctx, &d->reads, &rcap, (g0 + ng) * kDReads * sizeof(hq_dread), true,
-                      "hq_dstep reads");
-        size_t sc = d->gcap * 4;
-        if (!rc) rc = grow(ctx, &d->stamp, &sc, (g0 + ng) * 4, true, "hq_dstep stamps");
-        // the saved-state buffers only live within a step: grown without their contents
-        size_t gn = d->gcap * sizeof(hq_dgroup), rn = d->gcap * kDReads * sizeof(hq_dread);
-        if (!rc)
-            rc = grow(ctx, &d->groups_old, &gn, (g0 + ng) * sizeof(hq_dgroup), false,
-                      "hq_dstep saved groups");
-        if (!rc)
-            rc = grow(ctx, &d->reads_old, &rn, (g0 + ng) * kDReads * sizeof(hq_dread), false,
-                      "hq_dstep saved reads");
-        if (!rc) d->gcap = std::min({gc / sizeof(hq_dgroup), rcap / (kDReads * sizeof(hq_dread)),
-                                     sc / 4, gn / sizeof(hq_dgroup),
-                                     rn / (kDReads * sizeof(hq_dread))});
-    }
+    size_t mc = d->mcap * sizeof(hq_dmember);
+    if (!rc) rc = grow_groups(d, g0 + ng);
     for (uint64_t i = 0; i < ng; ++i)
         if (g[i].n_members > d->max_members) d->max_members = g[i].n_members;
     if (!rc && ng) {              // new stamps start at 0 (no step has listed them)
@@ -352,6 +357,40 @@ int hq_dstep_reserve_members(hq_dstep *d, uint64_t m0, uint64_t total) {
         rc = hq::check_hip(ctx, hipMemsetAsync(d->members + m0, 0, (total - m0) * sizeof(hq_dmember),
                                                ctx->stream), "hq_dstep members");
     return rc;
+}
+
+int hq_dstep_reserve_groups(hq_dstep *d, uint64_t total) {
+    hq_ctx *ctx = d->ctx;
+    int rc = hq::check_hip(ctx, hipSetDevice(ctx->device), "hipSetDevice");
+    if (rc || total <= d->n_groups) return rc;
+    rc = grow_groups(d, total);
+    if (!rc)                      // new stamps start at 0 (no step has listed them)
+        rc = hq::check_hip(ctx, hipMemsetAsync(d->stamp + d->n_groups, 0, (total - d->n_groups) * 4,
+                                               ctx->stream), "memset");
+    if (!rc) d->n_groups = total;
+    return rc;
+}
+
+int hq_dstep_members_spare(hq_dstep *d, hq_dmember **spare, uint64_t *capacity) {
+    hq_ctx *ctx = d->ctx;
+    *spare = nullptr;
+    *capacity = d->mcap;
+    int rc = hq::check_hip(ctx, hipSetDevice(ctx->device), "hipSetDevice");
+    if (rc || d->mcap == 0) return rc;
+    return hq::check_hip(ctx, hipMalloc(reinterpret_cast<void **>(spare), d->mcap * sizeof(hq_dmember)),
+                         "hq_dstep members (compaction)");
+}
+
+void hq_dstep_members_install(hq_dstep *d, hq_dmember *spare) {
+    if (!spare) return;
+    (void)hipSetDevice(d->ctx->device);
+    if (d->members) (void)hipFree(d->members);
+    d->members = spare;
+}
+
+void hq_dstep_members_drop(hq_dstep *d, hq_dmember *spare) {
+    (void)hipSetDevice(d->ctx->device);
+    if (spare) (void)hipFree(spare);
 }
 
 void hq_dstep_raise_max_members(hq_dstep *d, uint32_t n) {

@@ -79,9 +79,10 @@ __device__ inline GroupRef load_group(const hq_dgroup *g) {
     return r;
 }
 
-// the record checks the kernels rely on (the worker's own uploads satisfy them)
+// the record checks the kernels rely on (the worker's own uploads satisfy them); a record without
+// members is a vacant handle's tombstone (hq_worker_stop_groups), which sends nothing
 __device__ inline bool group_ok(uint64_t n_state_members, const GroupRef &g) {
-    return g.n_members >= 1 && g.n_members <= kDMembers && g.n_voting <= g.n_members &&
+    return (g.n_members >= 1 || !g.sends) && g.n_members <= kDMembers && g.n_voting <= g.n_members &&
            g.n_reads <= kDReads && (uint64_t)g.mem + g.n_members <= n_state_members;
 }
 

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "../../include/hipquorum.h"
+#include "hq_dstep.h"
 #include "hq_guard.h"
 #include "hq_stream.h"
 #include "hq_wire_codec.h"
@@ -180,6 +181,12 @@ class ClusterIndex {
 
 }  // namespace
 
+// The worker's lifecycle epoch (hq_dstep.h). The reference is weak: the wire also builds without
+// the worker's group store (a stand-alone check of this file over a stub worker), where no group
+// is ever stopped and the epoch stands at 0.
+uint64_t hq_worker_epoch(hq_worker *w) __attribute__((weak));
+static uint64_t epoch_of(hq_worker *w) { return w && hq_worker_epoch ? hq_worker_epoch(w) : 0; }
+
 struct hq_wire {
     uint64_t deployment_id = 0;
     std::string err;
@@ -187,10 +194,13 @@ struct hq_wire {
     std::vector<uint64_t> clusters;
     ClusterIndex cluster_index;
     // attached (hq_wire_attach): a record's key is the worker's handle, resolved as it is
-    // decoded through handle_of (cluster id -> handle, kept across steps: handles never change;
-    // only clusters the worker runs are kept in it)
+    // decoded through handle_of (cluster id -> handle, kept across steps; only clusters the
+    // worker runs are kept in it). Handles change only when groups are started or stopped
+    // (hq_worker_start_groups / _stop_groups): the worker's epoch then moves, and hq_wire_reset
+    // drops the cache
     hq_worker *worker = nullptr;
     ClusterIndex handle_of;
+    uint64_t worker_epoch = 0;         // the worker's epoch handle_of was filled under
     std::vector<uint64_t> pending;     // the cluster ids of a batch's records, before their keys
     hq_wire_stats stats{};
     // the assembled step input (valid until the next reset)
@@ -221,7 +231,7 @@ struct hq_wire {
     // hq_wire_add_batch and hq_wire_add_locals are all or nothing: unless `keep` is set, leaving
     // the scope (an exception, a refusal) puts recs, kcnt, clusters, cluster_index and stats back
     // to what they were when the entry began. Cluster ids newly cached in handle_of stay: a cache
-    // of facts that do not change. Nothing in it allocates.
+    // of facts that hold until the worker's epoch moves. Nothing in it allocates.
     struct Undo {
         hq_wire &w;
         const size_t r0, c0;
@@ -262,7 +272,16 @@ struct hq_wire {
         n_rejected = 0;
         worker = wk;
         handle_of = ClusterIndex();
+        worker_epoch = epoch_of(wk);
         kcnt.clear();
+    }
+    // attached: groups were started or stopped since the cache was filled, so a cluster may have
+    // left its handle or come back in another one
+    void follow_worker() noexcept {
+        const uint64_t now = epoch_of(worker);
+        if (now == worker_epoch) return;
+        handle_of = ClusterIndex();
+        worker_epoch = now;
     }
     // The counts in cnt (key k's at k + 1) made offsets, and the queue scattered by them into
     // perm: key k's records are perm[cnt[k] .. cnt[k + 1]), stable in arrival order. false (and
@@ -438,6 +457,7 @@ int hq_wire_attach_device(hq_wire *w, hq_worker *worker) {
 int hq_wire_reset(hq_wire *w) {
     return guarded(w, "hq_wire_reset", [&] {
         if (w->dev) hq_wire_dev_reset(w->dev);
+        w->follow_worker();
         w->batch_calls = 0;
         w->dev_queued = 0;
         w->rejected = nullptr;
@@ -541,7 +561,7 @@ static int add_batch_device(hq_wire *w, const uint8_t *bytes, size_t len) {
 // All or nothing: after an exception the queue, the per-handle counts, the clusters seen and the
 // stats are as before the call (hq_wire::Undo; in the device mode the stats, and what
 // hq_wire_dev_add_batch leaves of a batch it could not queue is its own). Cluster ids newly cached
-// in handle_of may stay: a cache of facts that do not change.
+// in handle_of may stay: a cache of facts that hold until the worker's epoch moves (hq_wire_reset).
 static int add_batch(hq_wire *w, const uint8_t *bytes, size_t len) {
     if (!bytes && len) return w->fail(HQ_E_INVAL, "hq_wire_add_batch: NULL bytes");
     if (w->dev) return add_batch_device(w, bytes, len);
@@ -734,8 +754,8 @@ static int step_sized(hq_wire *w, uint8_t *bytes, uint64_t cap, uint16_t *sizes1
     // counting sort of the records by handle, stable in arrival order; each handle's records
     // then taken category by category (node.handleEvents: local ReadIndex, received messages,
     // ticks, proposals)
-    // (the counts per handle were kept as the records were queued; handles only grow, so every
-    // queued key is below n)
+    // (the counts per handle were kept as the records were queued; the handle space only grows, so
+    // every queued key is below n)
     w->cnt.assign(n + 1, 0);
     std::copy(w->kcnt.begin(), w->kcnt.begin() + std::min<size_t>(w->kcnt.size(), n + 1), w->cnt.begin());
     if (!w->scatter([](const Rec &r) { return r.key; }))

@@ -272,9 +272,11 @@ struct hq_wire_dev {
     uint64_t n_msgs = 0;
     std::vector<StageBlock> stage;
     std::vector<uint32_t> rejected;
-    // the handle table: built from the worker's groups, extended when it has gained some
+    // the handle table: built from the worker's live groups, extended when it has gained some and
+    // rebuilt when groups were started or stopped (the worker's epoch has moved)
     std::vector<Slot> slots;
     uint64_t known = 0;                               // handles in the table
+    uint64_t epoch = 0;                               // the worker's epoch the table was built under
     bool has_empty = false;
     uint32_t empty_val = 0;
     DevBuf d_slots, d_spans, d_span_batch, d_bad, d_recs, d_cids, d_keys, d_vals, d_events, d_offsets,
@@ -328,21 +330,29 @@ struct hq_wire_dev {
         while (slots[s].key != kEmptyKey) s = (s + 1) & mask;
         slots[s] = Slot{id, h, 0};
     }
-    // the table holds every group of the worker (load <= 1/2); uploaded when it has changed
+    // the table holds every live group of the worker (load <= 1/2); uploaded when it has changed.
+    // Handles keep their clusters while the worker's epoch stands: the table is then only extended;
+    // once it has moved (hq_worker_start_groups / _stop_groups) the whole table is rebuilt from the
+    // live handles, so a stopped cluster resolves to nothing and a restarted one to its new handle
     int extend(uint64_t G) {
-        if (G == known && d_slots.p) return HQ_OK;
+        const uint64_t now = hq_worker_epoch(worker);
+        if (G == known && now == epoch && d_slots.p) return HQ_OK;
         size_t want = 1024;
         while (want < 2 * G) want *= 2;
         std::vector<uint64_t> ids(G);
+        std::vector<uint8_t> live(G);
         int rc = hq_worker_cluster_ids(worker, 0, G, ids.data());
+        if (!rc) rc = hq_worker_live_handles(worker, 0, G, live.data());
         if (rc) return fail(rc, "hq_wire_step_device: the worker's groups");
-        if (want != slots.size()) {                   // (handles never change: rebuilt from them)
+        if (want != slots.size() || now != epoch) {
             slots.assign(want, Slot{kEmptyKey, 0, 0});
             has_empty = false;
             known = 0;
         }
-        for (uint64_t h = known; h < G; ++h) insert(ids[h], (uint32_t)h);
+        for (uint64_t h = known; h < G; ++h)
+            if (live[h]) insert(ids[h], (uint32_t)h);
         known = G;
+        epoch = now;
         rc = ensure(d_slots, slots.size() * sizeof(Slot));
         if (!rc)
             rc = hip(hipMemcpyAsync(d_slots.p, slots.data(), slots.size() * sizeof(Slot),

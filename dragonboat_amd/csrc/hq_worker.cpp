@@ -103,7 +103,8 @@ int hq_worker::add_group(const hq_worker_group *g, const hq_member *members, uin
     return HQ_OK;
 }
 
-// One handle of a batched call's list: a group there is, in the 16 members the calls' records hold.
+// One handle of a batched call's list: a handle there is (a vacant one included: a tombstone record
+// without members), in the 16 members the calls' records hold.
 int hq_worker::check_listed(const char *entry, uint64_t h) {
     if (h >= groups.size()) return fail(HQ_E_INVAL, std::string(entry) + ": unknown group handle");
     if (groups[h].n_members > kDMembers)
@@ -162,6 +163,7 @@ void hq_worker_close(hq_worker *w) {
     if (w->hbw) hq_hbw_dev_close(w->hbw);
     if (w->cfg) hq_cfg_dev_close(w->cfg);
     if (w->grp) hq_groups_dev_close(w->grp);
+    if (w->poolc) hq_pool_dev_close(w->poolc);
     if (w->dstep) hq_dstep_close(w->dstep);
     if (w->ctx) {
         hq_sync(w->ctx);

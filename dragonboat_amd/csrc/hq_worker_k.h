@@ -7,6 +7,7 @@
 //   hq_worker_dev.cpp    the device worker's mirror and step; the step entry points
 //   hq_worker_hb.cpp     leader heartbeats, compact and as MessageBatch bytes
 //   hq_worker_lists.cpp  membership changes and the listed groups' fetch / resume
+//   hq_worker_lifecycle.cpp  groups started and stopped on a running worker, pool compaction
 // All of them plain C++ (no HIP headers): the worker is a client of the same ABI a cgo binding
 // would use. Every C entry's body runs inside `guarded` (hq_guard.h).
 //
@@ -28,6 +29,7 @@
 #include "hq_guard.h"
 #include "hq_heartbeat.h"
 #include "hq_heartbeat_wire.h"
+#include "hq_pool.h"
 
 namespace hq::wk {
 
@@ -58,6 +60,8 @@ enum : uint8_t {
     kSuspended = 1, kTouched = 2, kInWork = 4,
     kCommitDue = 8, kRiDue = 16, kVoteDue = 32, kCqDue = 64,
     kDue = kCommitDue | kRiDue | kVoteDue | kCqDue,
+    kVacant = 128,                        // a stopped group's handle: a tombstone (kSuspended, no
+                                          // members, follower) until a start reuses it
 };
 
 struct Group {
@@ -150,7 +154,12 @@ struct hq_worker {
     std::vector<Member> pool;
     std::vector<ReadQueue> rqs;
     std::vector<uint32_t> rq_free;
-    std::unordered_map<uint64_t, uint32_t> index;   // cluster_id -> handle
+    std::unordered_map<uint64_t, uint32_t> index;   // cluster_id -> handle (live groups only)
+    // group lifecycle (hq_worker_lifecycle.cpp): the vacant handles as a stack, the count of
+    // start / stop calls that changed anything, a device worker's compaction buffers (first call)
+    std::vector<uint32_t> vacant;
+    uint64_t epoch = 0;
+    hq_pool_dev *poolc = nullptr;
     // step scratch (`touched`: the groups a call has marked kTouched, unmarked before it returns)
     const hq_step_input *in = nullptr;
     std::vector<uint32_t> work, next_work, touched;
@@ -253,7 +262,38 @@ struct hq_worker {
     bool emit_group(const hq_dgroup &d, const hq_dread *r, const hq_dmember *m);
     int get_groups(uint64_t n, const uint32_t *handles, hq_groups_output *out);
     int set_groups(uint64_t n, const hq_worker_group *gs, const hq_member *ms, uint64_t *gpu_ns);
+    // group lifecycle (hq_worker_lifecycle.cpp)
+    bool live(uint64_t h) const { return h < groups.size() && !groups[h].has(hq::wk::kVacant); }
+    void reset_route_row(uint32_t h);
+    int scatter_records(const char *entry, uint64_t n, const uint32_t *hs, uint64_t *gpu_ns);
+    int start_groups(uint64_t n, const hq_worker_group *gs, const hq_member *ms, uint32_t *handles,
+                     uint64_t *gpu_ns);
+    int stop_groups(uint64_t n, const uint32_t *handles, uint64_t *gpu_ns);
+    uint64_t live_member_records() const;
+    int compact(uint64_t *gpu_ns);
 };
+
+// Marks each of a list's n groups kTouched while they are checked, so that a group listed twice
+// is seen, and always unmarks them (hq_worker_lists.cpp, hq_worker_lifecycle.cpp): handle_of(i, h) finds entry i's group (or fails), check(i, h)
+// is the entry's own check. A refused list changes nothing.
+template <class Handle, class Check>
+int hq_worker::check_distinct(uint64_t n, const char *twice, Handle &&handle_of, Check &&check) {
+    struct Unmark {
+        hq_worker &w;
+        ~Unmark() { w.unmark_touched(); }
+    } unmark{*this};
+    touched.clear();
+    touched.reserve(n);
+    for (uint64_t i = 0; i < n; ++i) {
+        uint32_t h = 0;
+        if (int rc = handle_of(i, h)) return rc;
+        if (groups[h].has(hq::wk::kTouched)) return fail(HQ_E_INVAL, twice);
+        if (int rc = check(i, h)) return rc;
+        groups[h].set(hq::wk::kTouched);
+        touched.push_back(h);
+    }
+    return HQ_OK;
+}
 
 // A C entry of the worker: HQ_E_INVAL for no worker, else the body's code, or an exception's
 // (hq_guard.h) with its message in hq_worker_last_error.

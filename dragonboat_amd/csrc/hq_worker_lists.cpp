@@ -5,28 +5,6 @@
 
 using namespace hq::wk;
 
-// Marks each of a list's n groups kTouched while they are checked, so that a group listed twice
-// is seen, and always unmarks them: handle_of(i, h) finds entry i's group (or fails), check(i, h)
-// is the entry's own check. A refused list changes nothing.
-template <class Handle, class Check>
-int hq_worker::check_distinct(uint64_t n, const char *twice, Handle &&handle_of, Check &&check) {
-    struct Unmark {
-        hq_worker &w;
-        ~Unmark() { w.unmark_touched(); }
-    } unmark{*this};
-    touched.clear();
-    touched.reserve(n);
-    for (uint64_t i = 0; i < n; ++i) {
-        uint32_t h = 0;
-        if (int rc = handle_of(i, h)) return rc;
-        if (groups[h].has(kTouched)) return fail(HQ_E_INVAL, twice);
-        if (int rc = check(i, h)) return rc;
-        groups[h].set(kTouched);
-        touched.push_back(h);
-    }
-    return HQ_OK;
-}
-
 // ------------------------------------------------------------------------------ membership ---
 // handleNodeConfigChange (raft.go:1540-1559) for the listed groups. The structure of a group —
 // member ids, roles, positions — is the host's own even while a device worker's mirror is stale,
@@ -182,7 +160,7 @@ int hq_worker::config_changes(uint64_t n, const hq_config_change *ch, hq_config_
         n, "hq_worker_config_changes: a group is listed twice",
         [&](uint64_t i, uint32_t &h) {
             h = ch[i].group;
-            return h < groups.size() ? HQ_OK : fail(HQ_E_INVAL, "hq_worker_config_changes: unknown group handle");
+            return live(h) ? HQ_OK : fail(HQ_E_INVAL, "hq_worker_config_changes: unknown group handle");
         },
         [&](uint64_t i, uint32_t h) {
             const hq_config_change &c = ch[i];
@@ -344,8 +322,11 @@ bool hq_worker::emit_group(const hq_dgroup &d, const hq_dread *r, const hq_dmemb
 
 int hq_worker::get_groups(uint64_t n, const uint32_t *handles, hq_groups_output *out) {
     // every check the host can make first: nothing is queued for a refused list
-    for (uint64_t i = 0; i < n; ++i)
-        if (int rc = check_listed("hq_worker_get_groups", handles ? handles[i] : i)) return rc;
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint64_t h = handles ? handles[i] : i;
+        if (int rc = check_listed("hq_worker_get_groups", h)) return rc;
+        if (!live(h)) return fail(HQ_E_INVAL, "hq_worker_get_groups: unknown group handle");
+    }
     for (auto *v : {&gg_granted, &gg_rejected, &gg_rconf}) v->clear();
     gg_groups.clear();
     gg_members.clear();

@@ -267,6 +267,15 @@ class GroupsOutput(ctypes.Structure):
                 ("gpu_ns", ctypes.c_uint64)]
 
 
+# group lifecycle (hq_worker_start_groups / _stop_groups / _pool_info / _compact)
+class PoolInfo(ctypes.Structure):
+    """Mirror of ``struct hq_worker_pool_info``."""
+
+    _fields_ = [("handles", ctypes.c_uint64), ("live_groups", ctypes.c_uint64),
+                ("vacant_handles", ctypes.c_uint64), ("member_records", ctypes.c_uint64),
+                ("live_member_records", ctypes.c_uint64), ("epoch", ctypes.c_uint64)]
+
+
 class WireBatchInfo(ctypes.Structure):
     _fields_ = [("n_messages", ctypes.c_uint64), ("deployment_id", ctypes.c_uint64),
                 ("source_address_len", ctypes.c_uint64), ("bin_ver", ctypes.c_uint32),
@@ -542,6 +551,10 @@ SIGNATURES = {
     "hq_worker_readback_count": (ctypes.c_int, [_vp, _u64p]),
     "hq_worker_get_groups": (ctypes.c_int, [_vp, ctypes.c_uint64, _vp, _vp]),
     "hq_worker_set_groups": (ctypes.c_int, [_vp, ctypes.c_uint64, _vp, _vp, _u64p]),
+    "hq_worker_start_groups": (ctypes.c_int, [_vp, ctypes.c_uint64, _vp, _vp, _vp, _u64p]),
+    "hq_worker_stop_groups": (ctypes.c_int, [_vp, ctypes.c_uint64, _vp, _u64p]),
+    "hq_worker_pool_info": (ctypes.c_int, [_vp, ctypes.POINTER(PoolInfo)]),
+    "hq_worker_compact": (ctypes.c_int, [_vp, _u64p]),
     "hq_synth_commit_dev": (ctypes.c_int, [_vp, ctypes.POINTER(SynthSpec), ctypes.POINTER(CommitArgs)]),
     "hq_synth_commit_lag_dev": (ctypes.c_int, [_vp, ctypes.POINTER(SynthSpec),
                                                ctypes.POINTER(LagArgs), _vp]),
@@ -1817,6 +1830,48 @@ class Worker:
         self._check(lib.hq_worker_set_groups(self.h, len(groups), _p(groups) if len(groups) else None,
                                              _p(members) if len(members) else None,
                                              ctypes.byref(ns)), "hq_worker_set_groups")
+        return ns.value
+
+    def start_groups(self, groups, members) -> np.ndarray:
+        """hq_worker_start_groups: StartCluster for every listed group (WORKER_GROUP_DTYPE records,
+        members of consecutive groups back to back), all validated before any is added; vacant
+        handles are reused, the most recently vacated first. A device worker writes the records
+        with one kernel and reads nothing back. Returns the groups' handles (uint32); the call's
+        gpu_ns is left in ``last_gpu_ns``."""
+        groups = np.ascontiguousarray(groups, WORKER_GROUP_DTYPE)
+        members = np.ascontiguousarray(members, MEMBER_DTYPE)
+        assert int(groups["n_members"].sum()) == len(members)
+        handles = np.zeros(len(groups), np.uint32)
+        ns = ctypes.c_uint64(0)
+        self._check(lib.hq_worker_start_groups(self.h, len(groups), _p(groups) if len(groups) else None,
+                                               _p(members) if len(members) else None,
+                                               _p(handles) if len(handles) else None,
+                                               ctypes.byref(ns)), "hq_worker_start_groups")
+        self.last_gpu_ns = ns.value
+        return handles
+
+    def stop_groups(self, handles) -> int:
+        """hq_worker_stop_groups: StopCluster for the listed handles (each live, listed once): the
+        clusters leave the index and their handles become vacant. Returns the call's gpu_ns (0 on
+        a host worker)."""
+        handles = np.ascontiguousarray(handles, np.uint32)
+        ns = ctypes.c_uint64(0)
+        self._check(lib.hq_worker_stop_groups(self.h, len(handles), _p(handles) if len(handles) else None,
+                                              ctypes.byref(ns)), "hq_worker_stop_groups")
+        return ns.value
+
+    def pool_info(self) -> dict:
+        """hq_worker_pool_info: 'handles', 'live_groups', 'vacant_handles', 'member_records',
+        'live_member_records', 'epoch'."""
+        out = PoolInfo()
+        self._check(lib.hq_worker_pool_info(self.h, ctypes.byref(out)), "hq_worker_pool_info")
+        return {name: int(getattr(out, name)) for name, _ in PoolInfo._fields_}
+
+    def compact(self) -> int:
+        """hq_worker_compact: closes the member pool's gaps (between steps). Returns the call's
+        gpu_ns (0 on a host worker or an already dense pool)."""
+        ns = ctypes.c_uint64(0)
+        self._check(lib.hq_worker_compact(self.h, ctypes.byref(ns)), "hq_worker_compact")
         return ns.value
 
     def readback_count(self) -> int:

@@ -1064,7 +1064,8 @@ int hq_worker_add_groups(hq_worker *w, const hq_worker_group *groups, uint64_t c
                          const hq_member *members);
 /* The handle of a cluster. */
 int hq_worker_find(hq_worker *w, uint64_t cluster_id, uint32_t *handle);
-/* The worker's groups (handles 0 .. *n - 1; ABI 21). */
+/* The worker's handle space (handles 0 .. *n - 1; ABI 21): every handle ever given out, the
+ * vacant ones of stopped groups included ("group lifecycle" below). */
 int hq_worker_group_count(hq_worker *w, uint64_t *n);
 /* Overwrite a group's state (re-sync after fallback); clears its read queue and votes and
  * resumes it. */
@@ -1353,7 +1354,8 @@ int hq_wire_add_locals(hq_wire *w, uint64_t n, const uint64_t *cluster_ids, cons
 /* ABI 21, the step worker's production feed: the step in the worker's handle order, straight into
  * a sized stream. hq_wire_attach binds a worker (before events are queued): from then on every
  * message's cluster is resolved to the worker's handle as its batch is decoded (through a table
- * the wire keeps across steps — handles never change), messages of clusters the worker does not
+ * the wire keeps across steps and drops at hq_wire_reset / rebuilds at hq_wire_step_device once
+ * hq_worker_start_groups / _stop_groups have changed the handles), messages of clusters the worker does not
  * run are dropped at once, and hq_wire_step_input / _step_stream are HQ_E_STATE. Each step:
  * hq_wire_reset, hq_wire_add_batch / hq_wire_add_locals, then hq_wire_step_sized writes every
  * handle h in 0 .. n - 1 (n = hq_worker_group_count) — its events in node.handleEvents order as
@@ -1746,6 +1748,68 @@ typedef struct hq_groups_output {
 int hq_worker_get_groups(hq_worker *w, uint64_t n, const uint32_t *handles, hq_groups_output *out);
 int hq_worker_set_groups(hq_worker *w, uint64_t n, const hq_worker_group *groups,
                          const hq_member *members, uint64_t *gpu_ns);
+
+/* ---------------------------------------------------------------- group lifecycle ----------- */
+/*
+ * Groups started and stopped on a running worker (NodeHost.StartCluster / StopCluster / StopNode)
+ * without a copy of the device state: hq_worker_readback_count does not move in any of the four
+ * calls, and a device worker writes the records where they live with the listed groups' scatter
+ * kernel. Host and device workers behave identically. Additions to ABI 21 (new symbols only);
+ * hq_worker_add_group(s) keep their behaviour (the readback on a stale mirror included) and never
+ * reuse a vacant handle.
+ *
+ * hq_worker_start_groups: group i's members follow group i - 1's in `members`, as for
+ * hq_worker_add_groups; per group the validation is hq_worker_add_group's. The cluster must not
+ * exist and must not be listed twice. All groups are validated before any is added: any failure
+ * is HQ_E_INVAL with nothing applied (unlike hq_worker_add_groups, which keeps the groups before
+ * the failing one). A new group takes a vacant handle if there is one, the most recently vacated
+ * first (a stack; hq_worker_stop_groups vacates its handles in list order), otherwise the next
+ * new handle; group i's handle goes to handles[i] (may be NULL). A started group is exactly what
+ * hq_worker_add_group makes: a candidate holds its own vote, the read queue is empty, it is not
+ * suspended. A reused handle's heartbeat route row is HQ_ROUTE_NONE.
+ *
+ * hq_worker_stop_groups: every handle must be live and listed once, otherwise HQ_E_INVAL with
+ * nothing applied. The cluster leaves the index (hq_worker_find, _get_group, _set_group and
+ * _set_groups answer "unknown cluster"), its pending reads, votes and members are dropped, its
+ * route row is reset to HQ_ROUTE_NONE and the handle becomes vacant. A suspended group may be
+ * stopped.
+ *
+ * A vacant handle is held as a tombstone record: suspended, no members, no voting slots,
+ * follower. A step that lists it gets its events back as `deferred`, as for any suspended group:
+ * no fallback record, no commit, no other output. Its heartbeat word is 0 and no heartbeat batch
+ * bytes are written for it. hq_worker_config_changes and hq_worker_get_groups (also with handles
+ * = NULL over a range that holds a vacancy) reject it as an unknown handle (HQ_E_INVAL, nothing
+ * applied). hq_worker_group_count keeps counting the handle space, vacancies included;
+ * hq_worker_set_heartbeat_routes may write a vacant row, a later start resets it.
+ *
+ * hq_worker_compact closes the member pool's gaps (the ranges left by stopped groups and by
+ * groups that moved to the pool's end): live groups keep their handles, the member ranges are
+ * packed in handle order with no spare room. Nothing observable changes but hq_worker_pool_info,
+ * where member_records == live_member_records afterwards. Called between steps; on an already
+ * dense pool it does nothing and returns HQ_OK. A device worker moves the records with one kernel
+ * (hq_pool.hip: k_pool_compact) into a second pool buffer.
+ *
+ * n = 0 is HQ_OK; NULL arrays with n > 0, a NULL worker or a NULL `out` are HQ_E_INVAL. *gpu_ns
+ * (may be NULL): device workers, the GPU time between the call's events; else 0.
+ */
+/* StartCluster for n groups at once; group i's members follow group i-1's in `members` (as
+ * hq_worker_add_groups). All groups are validated before any is added. */
+int hq_worker_start_groups(hq_worker *w, uint64_t n, const hq_worker_group *groups,
+                           const hq_member *members, uint32_t *handles /* [n] out, may be NULL */,
+                           uint64_t *gpu_ns /* may be NULL */);
+/* StopCluster / StopNode for the listed handles. */
+int hq_worker_stop_groups(hq_worker *w, uint64_t n, const uint32_t *handles, uint64_t *gpu_ns);
+
+typedef struct hq_worker_pool_info {
+    uint64_t handles;             /* the handle space: what hq_worker_group_count returns */
+    uint64_t live_groups, vacant_handles;
+    uint64_t member_records;      /* the pool's length */
+    uint64_t live_member_records; /* sum of the live groups' n_members */
+    uint64_t epoch;               /* +1 per start/stop call that changed anything */
+} hq_pool_info;   /* (the tag is the entry's name; a typedef of that name would collide with it) */
+int hq_worker_pool_info(hq_worker *w, hq_pool_info *out);
+/* Close the member pool's gaps (ranges left by stopped and by relocated groups). */
+int hq_worker_compact(hq_worker *w, uint64_t *gpu_ns);
 
 /* ---------------------------------------------------------------- synthetic inputs ---------- */
 

@@ -193,6 +193,68 @@ func (x *Worker) SetGroups(groups []GroupState, members []Member) (uint64, error
 	return uint64(ns), nil
 }
 
+// StartGroups starts the listed groups on the running worker (NodeHost.StartCluster); members
+// holds the groups' members back to back. Every group is validated before any is added: a
+// cluster that exists or is listed twice, or any invalid group, fails the call with nothing
+// applied. Vacant handles are reused, the most recently vacated first. A device worker writes the
+// records with one small kernel and reads nothing back. Returns the groups' handles and the
+// HIP-event time of the call (0 on a host worker).
+func (x *Worker) StartGroups(groups []GroupState, members []Member) ([]uint32, uint64, error) {
+	if len(groups) == 0 {
+		return nil, 0, nil
+	}
+	var mp *C.hq_member
+	if len(members) > 0 {
+		mp = &members[0]
+	}
+	handles := make([]uint32, len(groups))
+	var ns C.uint64_t
+	if rc := C.hq_worker_start_groups(x.w, C.uint64_t(len(groups)), &groups[0], mp,
+		(*C.uint32_t)(unsafe.Pointer(&handles[0])), &ns); rc != C.HQ_OK {
+		return nil, 0, x.err(rc)
+	}
+	return handles, uint64(ns), nil
+}
+
+// StopGroups stops the listed groups (NodeHost.StopCluster / StopNode): every handle must be live
+// and listed once, else nothing is applied. The clusters leave the worker's index and their
+// handles become vacant: a later step that lists one gets its events back as deferred. Returns
+// the HIP-event time of the call (0 on a host worker).
+func (x *Worker) StopGroups(handles []uint32) (uint64, error) {
+	if len(handles) == 0 {
+		return 0, nil
+	}
+	var ns C.uint64_t
+	if rc := C.hq_worker_stop_groups(x.w, C.uint64_t(len(handles)),
+		(*C.uint32_t)(unsafe.Pointer(&handles[0])), &ns); rc != C.HQ_OK {
+		return 0, x.err(rc)
+	}
+	return uint64(ns), nil
+}
+
+// PoolInfo is hq_worker_pool_info: the handle space and the member pool of the worker.
+type PoolInfo = C.hq_pool_info
+
+// PoolInfo reports the worker's handle space (live and vacant handles), its member pool (records
+// held and records of live groups: their difference is what Compact frees) and its lifecycle epoch.
+func (x *Worker) PoolInfo() (info PoolInfo, err error) {
+	if rc := C.hq_worker_pool_info(x.w, &info); rc != C.HQ_OK {
+		return info, x.err(rc)
+	}
+	return info, nil
+}
+
+// Compact closes the member pool's gaps (the ranges of stopped and of relocated groups), between
+// steps; handles do not change. Returns the HIP-event time of the call (0 on a host worker or an
+// already dense pool).
+func (x *Worker) Compact() (uint64, error) {
+	var ns C.uint64_t
+	if rc := C.hq_worker_compact(x.w, &ns); rc != C.HQ_OK {
+		return 0, x.err(rc)
+	}
+	return uint64(ns), nil
+}
+
 // Output is one step's results; the lists live in the worker's pinned buffers and are valid
 // until the worker's next step.
 type Output struct {
