@@ -164,6 +164,7 @@ void hq_worker_close(hq_worker *w) {
     if (w->cfg) hq_cfg_dev_close(w->cfg);
     if (w->grp) hq_groups_dev_close(w->grp);
     if (w->poolc) hq_pool_dev_close(w->poolc);
+    if (w->tickd) hq_tick_dev_close(w->tickd);
     if (w->dstep) hq_dstep_close(w->dstep);
     if (w->ctx) {
         hq_sync(w->ctx);
@@ -230,6 +231,7 @@ int hq_worker_set_group(hq_worker *w, const hq_worker_group *g, const hq_member 
         rc = w->load_group(n, g, members, false);
         if (rc) return rc;
         w->groups[it->second] = n;
+        w->tick_touch(it->second);                  // (its timer comes back reset)
         if (w->dstep && it->second < w->dev_groups) w->dirty.push_back(it->second);
         return HQ_OK;
     });

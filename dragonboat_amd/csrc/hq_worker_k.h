@@ -8,6 +8,7 @@
 //   hq_worker_hb.cpp     leader heartbeats, compact and as MessageBatch bytes
 //   hq_worker_lists.cpp  membership changes and the listed groups' fetch / resume
 //   hq_worker_lifecycle.cpp  groups started and stopped on a running worker, pool compaction
+//   hq_worker_tick.cpp   the Raft timers: one tick of every group, the listed timers' get / set
 // All of them plain C++ (no HIP headers): the worker is a client of the same ABI a cgo binding
 // would use. Every C entry's body runs inside `guarded` (hq_guard.h).
 //
@@ -30,6 +31,7 @@
 #include "hq_heartbeat.h"
 #include "hq_heartbeat_wire.h"
 #include "hq_pool.h"
+#include "hq_tick.h"
 
 namespace hq::wk {
 
@@ -160,6 +162,15 @@ struct hq_worker {
     std::vector<uint32_t> vacant;
     uint64_t epoch = 0;
     hq_pool_dev *poolc = nullptr;
+    // raft timers (hq_worker_tick.cpp): the checked config (tick_on: one was set); a host worker's
+    // timers, one per handle, its contact bitmap and its due lists; a device worker's timer array
+    // and buffers (first call) and the handles whose timers come back reset (or all of them)
+    bool tick_on = false, tick_reset_all = false;
+    hq_tick_params tick_p{};
+    std::vector<hq_tick_timer> timers;
+    std::vector<uint32_t> tk_contact, tk_lists[kTickLists];
+    hq_tick_dev *tickd = nullptr;
+    std::vector<uint32_t> tick_resets;
     // step scratch (`touched`: the groups a call has marked kTouched, unmarked before it returns)
     const hq_step_input *in = nullptr;
     std::vector<uint32_t> work, next_work, touched;
@@ -271,6 +282,13 @@ struct hq_worker {
     int stop_groups(uint64_t n, const uint32_t *handles, uint64_t *gpu_ns);
     uint64_t live_member_records() const;
     int compact(uint64_t *gpu_ns);
+    // raft timers (hq_worker_tick.cpp)
+    void tick_touch(uint32_t h);
+    int tick_flush(const char *entry);
+    int set_tick_config(const hq_tick_config *cfg);
+    int tick(uint64_t n_contact, const uint32_t *contact, hq_tick_output *out);
+    int get_timers(uint64_t n, const uint32_t *handles, hq_timer *out);
+    int set_timers(uint64_t n, const uint32_t *handles, const hq_timer *ts);
 };
 
 // Marks each of a list's n groups kTouched while they are checked, so that a group listed twice

@@ -115,6 +115,7 @@ int hq_worker::start_groups(uint64_t n, const hq_worker_group *gs, const hq_memb
         }
         index.emplace(g.cluster_id, h);
         reset_route_row(h);
+        tick_touch(h);                              // (a reused handle's timer comes back reset)
         hs[i] = h;
     }
     ++epoch;

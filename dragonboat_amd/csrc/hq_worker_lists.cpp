@@ -431,6 +431,7 @@ int hq_worker::set_groups(uint64_t n, const hq_worker_group *gs, const hq_member
         Group g = groups[h];
         if ((rc = load_group(g, gs + i, ms + off, false))) return rc;   // (checked above: cannot fail)
         groups[h] = g;
+        tick_touch(h);                              // (its timer comes back reset)
         off += gs[i].n_members;
         if (!dstep) continue;
         hq_dgroup dg;

@@ -276,6 +276,29 @@ class PoolInfo(ctypes.Structure):
                 ("live_member_records", ctypes.c_uint64), ("epoch", ctypes.c_uint64)]
 
 
+# raft timers (hq_worker_set_tick_config / _tick / _get_timers / _set_timers, hq_tick_timeout)
+class TickConfig(ctypes.Structure):
+    """Mirror of ``hq_tick_config``."""
+
+    _fields_ = [("election_rtt", ctypes.c_uint32), ("heartbeat_rtt", ctypes.c_uint32),
+                ("check_quorum", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("seed", ctypes.c_uint64)]
+
+
+class TickOutput(ctypes.Structure):
+    """Mirror of ``hq_tick_output``."""
+
+    _fields_ = [("check_quorum", _vp), ("n_check_quorum", ctypes.c_uint64),
+                ("heartbeat", _vp), ("n_heartbeat", ctypes.c_uint64),
+                ("election", _vp), ("n_election", ctypes.c_uint64),
+                ("n_ticked", ctypes.c_uint64), ("gpu_ns", ctypes.c_uint64)]
+
+
+TIMER_DTYPE = np.dtype([("election_tick", "<u4"), ("heartbeat_tick", "<u4"),
+                        ("randomized_timeout", "<u4"), ("reserved", "<u4")], align=True)
+assert (ctypes.sizeof(TickConfig), ctypes.sizeof(TickOutput), TIMER_DTYPE.itemsize) == (24, 64, 16)
+
+
 class WireBatchInfo(ctypes.Structure):
     _fields_ = [("n_messages", ctypes.c_uint64), ("deployment_id", ctypes.c_uint64),
                 ("source_address_len", ctypes.c_uint64), ("bin_ver", ctypes.c_uint32),
@@ -555,6 +578,12 @@ SIGNATURES = {
     "hq_worker_stop_groups": (ctypes.c_int, [_vp, ctypes.c_uint64, _vp, _u64p]),
     "hq_worker_pool_info": (ctypes.c_int, [_vp, ctypes.POINTER(PoolInfo)]),
     "hq_worker_compact": (ctypes.c_int, [_vp, _u64p]),
+    "hq_worker_set_tick_config": (ctypes.c_int, [_vp, ctypes.POINTER(TickConfig)]),
+    "hq_worker_tick": (ctypes.c_int, [_vp, ctypes.c_uint64, _vp, ctypes.POINTER(TickOutput)]),
+    "hq_tick_timeout": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
+                                       ctypes.c_uint32, ctypes.c_uint32]),
+    "hq_worker_get_timers": (ctypes.c_int, [_vp, ctypes.c_uint64, _vp, _vp]),
+    "hq_worker_set_timers": (ctypes.c_int, [_vp, ctypes.c_uint64, _vp, _vp]),
     "hq_synth_commit_dev": (ctypes.c_int, [_vp, ctypes.POINTER(SynthSpec), ctypes.POINTER(CommitArgs)]),
     "hq_synth_commit_lag_dev": (ctypes.c_int, [_vp, ctypes.POINTER(SynthSpec),
                                                ctypes.POINTER(LagArgs), _vp]),
@@ -584,6 +613,12 @@ class HQError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"hipquorum error {code}: {msg}")
         self.code = code
+
+
+def tick_timeout(seed: int, cluster_id: int, term: int, state: int, election_rtt: int) -> int:
+    """hq_tick_timeout: the randomized election timeout, in [election_rtt, 2 election_rtt), of a
+    group at (term, state) under a tick config's seed."""
+    return lib.hq_tick_timeout(seed, cluster_id, term, state, election_rtt)
 
 
 def device_count() -> int:
@@ -1873,6 +1908,64 @@ class Worker:
         ns = ctypes.c_uint64(0)
         self._check(lib.hq_worker_compact(self.h, ctypes.byref(ns)), "hq_worker_compact")
         return ns.value
+
+    def set_tick_config(self, election_rtt, heartbeat_rtt, check_quorum=True, seed=0):
+        """hq_worker_set_tick_config: the worker's electionTimeout / heartbeatTimeout in ticks,
+        whether leaders run CheckQuorum, and the seed of the randomized timeouts. Resets every
+        timer."""
+        cfg = TickConfig(election_rtt, heartbeat_rtt, int(check_quorum), 0, seed)
+        self._check(lib.hq_worker_set_tick_config(self.h, ctypes.byref(cfg)),
+                    "hq_worker_set_tick_config")
+
+    def tick(self, contact=None, copy=True):
+        """hq_worker_tick: one tick of every live, unsuspended group; `contact` (uint32 handles,
+        repeats allowed) the groups that heard from their leader since the last tick. Returns a
+        dict: 'check_quorum', 'heartbeat', 'election' (uint32 handles, ascending: the groups whose
+        step carries HQ_EV_CHECK_QUORUM, the list for heartbeats(), the groups whose step carries
+        HQ_EV_ELECTION), 'n_ticked', 'gpu_ns'. With copy=False the lists are views of the
+        worker's buffers, valid until its next tick."""
+        n, cp = 0, None
+        if contact is not None:
+            contact = np.ascontiguousarray(contact, np.uint32)
+            n, cp = len(contact), _p(contact) if len(contact) else None
+        out = TickOutput()
+        self._check(lib.hq_worker_tick(self.h, n, cp, ctypes.byref(out)), "hq_worker_tick")
+        res = {"n_ticked": out.n_ticked, "gpu_ns": out.gpu_ns}
+        dt = np.dtype("<u4")
+        for name in ("check_quorum", "heartbeat", "election"):
+            count = getattr(out, "n_" + name)
+            if count == 0:
+                res[name] = np.zeros(0, dt)
+                continue
+            buf = (ctypes.c_char * (count * 4)).from_address(getattr(out, name))
+            res[name] = np.frombuffer(buf, dt).copy() if copy else np.frombuffer(buf, dt)
+        return res
+
+    def get_timers(self, handles=None) -> np.ndarray:
+        """hq_worker_get_timers: the timers of the listed handles (uint32, repeats allowed; None:
+        every handle in order) as a TIMER_DTYPE array; a timer with a pending reset comes as
+        reset."""
+        if handles is None:
+            n, hp = self.group_count(), None
+        else:
+            handles = np.ascontiguousarray(handles, np.uint32)
+            n, hp = len(handles), _p(handles) if len(handles) else None
+        out = np.zeros(n, TIMER_DTYPE)
+        self._check(lib.hq_worker_get_timers(self.h, n, hp, _p(out) if n else None),
+                    "hq_worker_get_timers")
+        return out
+
+    def set_timers(self, handles, timers):
+        """hq_worker_set_timers: the listed handles' (uint32, each once; None: handles 0 .. n - 1)
+        counters from a TIMER_DTYPE array; randomized_timeout 0 draws it by the formula."""
+        timers = np.ascontiguousarray(timers, TIMER_DTYPE)
+        n, hp = len(timers), None
+        if handles is not None:
+            handles = np.ascontiguousarray(handles, np.uint32)
+            assert len(handles) == n
+            hp = _p(handles) if n else None
+        self._check(lib.hq_worker_set_timers(self.h, n, hp, _p(timers) if n else None),
+                    "hq_worker_set_timers")
 
     def readback_count(self) -> int:
         """hq_worker_readback_count: how often the device-resident state was copied back."""

@@ -1811,6 +1811,113 @@ int hq_worker_pool_info(hq_worker *w, hq_pool_info *out);
 /* Close the member pool's gaps (ranges left by stopped and by relocated groups). */
 int hq_worker_compact(hq_worker *w, uint64_t *gpu_ns);
 
+/* ---------------------------------------------------------------- raft timers --------------- */
+/*
+ * One tick of every group of a worker (raft.tick / leaderTick / nonLeaderTick, raft.go:525-636)
+ * from counters kept beside the quorum state, and the three lists of what is due: the handles
+ * whose step carries HQ_EV_CHECK_QUORUM, the handles to pass to hq_worker_heartbeats /
+ * _heartbeat_batches, and the handles whose step carries HQ_EV_ELECTION. Host and device workers
+ * behave identically; a device worker keeps the timers in a device array of 16 bytes per handle
+ * and ticks with hq_tick.hip's kernels over the resident (term, state), so that nothing is read
+ * back: hq_worker_readback_count moves in none of these calls. Additions to ABI 21 (new symbols
+ * only); the step, the heartbeat entries and the lifecycle entries keep their behaviour.
+ *
+ * hq_worker_set_tick_config: one config per worker (a NodeHost's groups share their RTT
+ * settings). Checked in this order: a NULL worker, a NULL cfg, then 1 <= election_rtt <= 32767,
+ * 1 <= heartbeat_rtt <= 65535, check_quorum 0 or 1, reserved 0; each failure is HQ_E_INVAL with
+ * the earlier config kept. Setting a config, the same one included, resets every timer.
+ *
+ * A group's timer is election_tick, heartbeat_tick and randomized_timeout (electionTick,
+ * heartbeatTick, randomizedElectionTimeout) with the (term, state) they were counted under.
+ *
+ * hq_worker_tick advances every live group that is not suspended by exactly one tick (the caller
+ * calls it once per LocalTick: the reference applies Election / CheckQuorum between two ticks).
+ * HQ_E_STATE before a config was set. Per group, in this order:
+ *   1. Reset: election_tick = heartbeat_tick = 0 and randomized_timeout drawn again, when since
+ *      the previous tick the group's (term, state) changed, its handle was started, added,
+ *      re-synced (hq_worker_set_group(s)) or un-suspended, or the config was set. This is
+ *      raft.reset (raft.go:991-1023) observed at the next tick instead of at the event; the
+ *      counters after the tick are the same either way, because within one term a state never
+ *      recurs (becomeCandidate raises the term; leader -> follower at the same term is one-way).
+ *   2. Contact: a group listed in `contact` that is not a leader gets election_tick = 0
+ *      (leaderIsAvailable, raft.go:1859-1861: the Heartbeat / Replicate messages that cause it are
+ *      handled on the CPU, so the caller lists those handles). A leader in the list is ignored, a
+ *      handle may be listed twice.
+ *   3. A leader (leaderTick): election_tick++; at election_rtt it returns to 0 and, with
+ *      check_quorum, the handle is listed in `check_quorum`. Then heartbeat_tick++; at
+ *      heartbeat_rtt it returns to 0 and the handle is listed in `heartbeat`. A handle may be in
+ *      both lists.
+ *   4. A follower or candidate (nonLeaderTick): election_tick++; at randomized_timeout it returns
+ *      to 0 and the handle is listed in `election` (the caller still filters
+ *      hasConfigChangeToApply, as for HQ_EV_ELECTION).
+ * Suspended groups and vacant handles are not ticked and appear in no list (the CPU raft ticks a
+ * group it took over); they come back reset. A contact handle at or beyond the group count, or a
+ * vacant one, is HQ_E_INVAL with nothing ticked. n_contact = 0 needs no `contact`; a NULL `out`,
+ * or a NULL `contact` with n_contact > 0, is HQ_E_INVAL. A device worker first uploads pending
+ * hq_worker_add_group / _set_group changes, as a step does.
+ *
+ * The caller's order within a tick interval: hq_worker_tick; then the step, which carries
+ * HQ_EV_CHECK_QUORUM / HQ_EV_ELECTION for the listed handles; then
+ * hq_worker_heartbeats(n_heartbeat, heartbeat, ...). A leader that the step's CheckQuorum demoted
+ * then sends nothing, as in the reference, which handles CheckQuorum before LeaderHeartbeat within
+ * a tick (raft.go:590-612).
+ *
+ * Each list holds handles in strictly ascending order. The lists are the worker's (pinned host
+ * memory for a device worker), valid until its next hq_worker_tick or close; they are not the
+ * step's or the heartbeats' buffers.
+ *
+ * randomized_timeout is drawn by hq_tick_timeout, uniform in [E, 2E) for E = election_rtt (the
+ * reference draws from a locked global RNG, raft.go:633-636, whose contract is this range). With
+ * all arithmetic modulo 2^64:
+ *     x = seed ^ cluster_id * 0x9E3779B97F4A7C15 ^ term * 0xBF58476D1CE4E5B9 ^ state
+ *     z = x + 0x9E3779B97F4A7C15
+ *     z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9
+ *     z = (z ^ z >> 27) * 0x94D049BB133111EB
+ *     z ^= z >> 31
+ *     randomized_timeout = E + z % E
+ * hq_tick_timeout is stateless and needs no worker. It returns the value itself (at most 65533; an
+ * int, as every exported entry of this header returns), and 0, which is no timeout, for an
+ * election_rtt outside 1 .. 32767.
+ *
+ * hq_worker_get_timers / _set_timers hand a group over or back with its counters. `handles` NULL
+ * means handles 0 .. n - 1; n = 0 is HQ_OK; HQ_E_STATE before a config was set; a NULL `out` /
+ * `timers` with n > 0 is HQ_E_INVAL; a handle beyond the group count or a vacant one is HQ_E_INVAL
+ * with nothing written or applied. get: handles may repeat; a timer with a pending reset (a
+ * suspended group's included) is returned as reset. set: a handle listed twice is HQ_E_INVAL; it
+ * clears a pending reset and takes the group's current (term, state) as the one the counters were
+ * counted under; randomized_timeout 0 means "draw by the formula", any other value must lie in
+ * [E, 2E); election_tick < 2E, heartbeat_tick < heartbeat_rtt and reserved = 0 are required
+ * whatever the group's state (a counter at or past its limit fires at the next tick). Otherwise
+ * HQ_E_INVAL with nothing applied. A timer set on a suspended group is reset when the group comes
+ * back.
+ *
+ * Not covered (the caller's): quiesce, timeToAbortLeaderTransfer, the rate-limit and in-memory-GC
+ * ticks, selfRemoved, per-group RTT settings, more than one tick per call.
+ */
+typedef struct hq_tick_config {
+    uint32_t election_rtt;    /* electionTimeout */
+    uint32_t heartbeat_rtt;   /* heartbeatTimeout */
+    uint32_t check_quorum;    /* 0 or 1 */
+    uint32_t reserved;
+    uint64_t seed;
+} hq_tick_config;
+typedef struct hq_tick_output {
+    const uint32_t *check_quorum; uint64_t n_check_quorum;
+    const uint32_t *heartbeat;    uint64_t n_heartbeat;
+    const uint32_t *election;     uint64_t n_election;
+    uint64_t n_ticked;            /* groups advanced */
+    uint64_t gpu_ns;              /* device workers: HIP-event time of the call's kernels, else 0 */
+} hq_tick_output;
+typedef struct hq_timer {
+    uint32_t election_tick, heartbeat_tick, randomized_timeout, reserved;
+} hq_timer;
+int hq_worker_set_tick_config(hq_worker *w, const hq_tick_config *cfg);
+int hq_worker_tick(hq_worker *w, uint64_t n_contact, const uint32_t *contact, hq_tick_output *out);
+int hq_tick_timeout(uint64_t seed, uint64_t cluster_id, uint64_t term, uint32_t state,
+                    uint32_t election_rtt);
+int hq_worker_get_timers(hq_worker *w, uint64_t n, const uint32_t *handles, hq_timer *out);
+int hq_worker_set_timers(hq_worker *w, uint64_t n, const uint32_t *handles, const hq_timer *timers);
+
 /* ---------------------------------------------------------------- synthetic inputs ---------- */
 
 /*

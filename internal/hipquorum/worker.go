@@ -255,6 +255,107 @@ func (x *Worker) Compact() (uint64, error) {
 	return uint64(ns), nil
 }
 
+// SetTickConfig sets the worker's Raft timer settings (hq_worker_set_tick_config): electionRTT and
+// heartbeatRTT are config.ElectionRTT / HeartbeatRTT in ticks, checkQuorum config.CheckQuorum, seed
+// the seed of the randomized election timeouts. One config per worker; setting it resets every
+// timer.
+func (x *Worker) SetTickConfig(electionRTT, heartbeatRTT uint32, checkQuorum bool, seed uint64) error {
+	cfg := C.hq_tick_config{election_rtt: C.uint32_t(electionRTT), heartbeat_rtt: C.uint32_t(heartbeatRTT),
+		seed: C.uint64_t(seed)}
+	if checkQuorum {
+		cfg.check_quorum = 1
+	}
+	if rc := C.hq_worker_set_tick_config(x.w, &cfg); rc != C.HQ_OK {
+		return x.err(rc)
+	}
+	return nil
+}
+
+// TickOutput is what is due after one tick (hq_worker_tick): three lists of worker handles in
+// ascending order, in the worker's buffers (pinned host memory on a device worker) and valid until
+// its next Tick.
+type TickOutput struct {
+	c C.hq_tick_output
+}
+
+func tickList(p *C.uint32_t, n C.uint64_t) []uint32 {
+	if n == 0 {
+		return nil
+	}
+	return unsafe.Slice((*uint32)(unsafe.Pointer(p)), int(n))
+}
+
+// CheckQuorum lists the leaders whose step carries HQ_EV_CHECK_QUORUM, Election the followers and
+// candidates whose step carries HQ_EV_ELECTION (the caller still filters hasConfigChangeToApply),
+// Heartbeat the leaders to pass to Heartbeats / HeartbeatBatches after that step.
+func (o *TickOutput) CheckQuorum() []uint32 { return tickList(o.c.check_quorum, o.c.n_check_quorum) }
+func (o *TickOutput) Heartbeat() []uint32   { return tickList(o.c.heartbeat, o.c.n_heartbeat) }
+func (o *TickOutput) Election() []uint32    { return tickList(o.c.election, o.c.n_election) }
+
+// Ticked is the number of groups advanced, GPUNanos the HIP-event time of the call's kernels (0 on
+// a host worker).
+func (o *TickOutput) Ticked() uint64   { return uint64(o.c.n_ticked) }
+func (o *TickOutput) GPUNanos() uint64 { return uint64(o.c.gpu_ns) }
+
+// Tick advances every live, unsuspended group by one tick (raft.tick, raft.go:525-636), once per
+// LocalTick. contact lists the handles of the followers that heard from their leader since the
+// last Tick (leaderIsAvailable, raft.go:1859-1861; repeats allowed). The caller's order within a
+// tick interval: Tick, then the step with the CheckQuorum / Election events of the listed handles,
+// then Heartbeats over Heartbeat(). A device worker ticks its resident state with three small
+// kernels: nothing of the state is read back.
+func (x *Worker) Tick(contact []uint32) (*TickOutput, error) {
+	var cp *C.uint32_t
+	if len(contact) > 0 {
+		cp = (*C.uint32_t)(unsafe.Pointer(&contact[0]))
+	}
+	o := &TickOutput{}
+	if rc := C.hq_worker_tick(x.w, C.uint64_t(len(contact)), cp, &o.c); rc != C.HQ_OK {
+		return nil, x.err(rc)
+	}
+	return o, nil
+}
+
+// Timer is hq_timer: a group's electionTick, heartbeatTick and randomizedElectionTimeout.
+type Timer = C.hq_timer
+
+// TickTimeout is the randomized election timeout, in [electionRTT, 2 electionRTT), the worker draws
+// for a group at (term, state) under seed (hq_tick_timeout).
+func TickTimeout(seed, clusterID, term uint64, state, electionRTT uint32) uint32 {
+	return uint32(C.hq_tick_timeout(C.uint64_t(seed), C.uint64_t(clusterID), C.uint64_t(term),
+		C.uint32_t(state), C.uint32_t(electionRTT)))
+}
+
+// GetTimers fetches the timers of the listed handles (repeats allowed), what the CPU raft takes
+// over with a suspended group; a timer with a pending reset comes as reset.
+func (x *Worker) GetTimers(handles []uint32) ([]Timer, error) {
+	if len(handles) == 0 {
+		return nil, nil
+	}
+	out := make([]Timer, len(handles))
+	if rc := C.hq_worker_get_timers(x.w, C.uint64_t(len(handles)),
+		(*C.uint32_t)(unsafe.Pointer(&handles[0])), &out[0]); rc != C.HQ_OK {
+		return nil, x.err(rc)
+	}
+	return out, nil
+}
+
+// SetTimers hands the listed handles (each once) back with their counters, after SetGroups: the
+// counters continue under the group's current term and state; a randomized_timeout of 0 is drawn
+// by the worker. Every entry is validated before any is applied.
+func (x *Worker) SetTimers(handles []uint32, timers []Timer) error {
+	if len(handles) == 0 {
+		return nil
+	}
+	if len(timers) != len(handles) {
+		return fmt.Errorf("hipquorum: %d timers for %d handles", len(timers), len(handles))
+	}
+	if rc := C.hq_worker_set_timers(x.w, C.uint64_t(len(handles)),
+		(*C.uint32_t)(unsafe.Pointer(&handles[0])), &timers[0]); rc != C.HQ_OK {
+		return x.err(rc)
+	}
+	return nil
+}
+
 // Output is one step's results; the lists live in the worker's pinned buffers and are valid
 // until the worker's next step.
 type Output struct {
