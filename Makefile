@@ -15,7 +15,7 @@ SRCS := $(CSRC)/hq_runtime.hip $(CSRC)/hq_commit.hip $(CSRC)/hq_commit_tiles.hip
         $(CSRC)/hq_engine.hip $(CSRC)/hq_wire_frame.cpp $(CSRC)/hq_wire_dev.hip \
         $(CSRC)/hq_heartbeat.hip $(CSRC)/hq_heartbeat_wire.hip $(CSRC)/hq_wire_frame_dev.hip \
         $(CSRC)/hq_config.hip $(CSRC)/hq_groups.hip $(CSRC)/hq_tick.hip \
-        $(CSRC)/hq_worker_tick.cpp
+        $(CSRC)/hq_worker_tick.cpp $(CSRC)/hq_hb_received.hip $(CSRC)/hq_worker_hbrecv.cpp
 OBJS := $(patsubst $(CSRC)/%,$(LIBDIR)/%.o,$(basename $(SRCS)))
 DEPS := $(wildcard $(CSRC)/*.h) include/hipquorum.h
 CXX ?= g++

@@ -145,14 +145,18 @@ int hq_tick_dev_contact(hq_tick_dev *t, uint64_t n_groups, uint32_t **bitmap);
 // success the next run, get or set is queued behind it; a failure has waited for the stream.
 int hq_tick_dev_invalidate(hq_tick_dev *t, uint64_t n_groups, bool all, uint64_t n, const uint32_t *handles);
 // One tick of every group of `st` (the timers were grown to st->n_groups); with_contact: the
-// bitmap handed out by hq_tick_dev_contact. *out's lists are t's pinned buffers, valid until its
+// bitmap handed out by hq_tick_dev_contact. `pending` (or NULL): a device bitmap of at least
+// st->n_groups bits whose set bits are contacts too (hq_hb_received.hip's); its first
+// ceil(n_groups / 32) words are zeroed behind the kernels. *out's lists are t's pinned buffers, valid until its
 // next run. Waits for the kernels, also when something failed.
 int hq_tick_dev_run(hq_tick_dev *t, const hq_dstate_view *st, const hq_tick_params *p, bool with_contact,
-                    hq_tick_output *out);
+                    uint32_t *pending, hq_tick_output *out);
 // out[i] <- the timer of handles[i] (host memory; NULL: of handle i), as tick_public gives it; the
 // timer of handles[i] (distinct) <- timers[i], as tick_from_public makes it. 0 < n < 2^32.
-// HQ_E_INVAL with *error set when the kernel refused a handle. Both wait for their kernel.
+// `pending` as for the run: get returns a non-leader whose bit is set with election_tick 0, set
+// clears the bits of its handles. HQ_E_INVAL with *error set when the kernel refused a handle. Both
+// wait for their kernel.
 int hq_tick_dev_get(hq_tick_dev *t, const hq_dstate_view *st, const hq_tick_params *p, uint64_t n,
-                    const uint32_t *handles, hq_timer *out, uint32_t *error);
+                    const uint32_t *handles, hq_timer *out, uint32_t *pending, uint32_t *error);
 int hq_tick_dev_set(hq_tick_dev *t, const hq_dstate_view *st, const hq_tick_params *p, uint64_t n,
-                    const uint32_t *handles, const hq_timer *timers, uint32_t *error);
+                    const uint32_t *handles, const hq_timer *timers, uint32_t *pending, uint32_t *error);

@@ -7,8 +7,9 @@
 //   k_tick       one lane per handle, 256 handles (a tile) per workgroup: the second and fourth 16
 //                bytes of the group record (term | state, flags; a wave's loads are 64-byte
 //                strided, two quads of every 64-byte record), the cluster id only of a group whose
-//                timer is reset, the timer as one 16-byte load, the contact bit from a bitmap, the
-//                transition of hq_tick.h, the timer back as one 16-byte store. What the tick did
+//                timer is reset, the timer as one 16-byte load, the contact bit from two bitmaps
+//                (the call's staged list, and the contacts hq_hb_received.hip marked on the
+//                device since the last tick), the transition of hq_tick.h, the timer back as one 16-byte store. What the tick did
 //                goes out as four wave ballots (check-quorum, heartbeat, election, ticked: 32 bytes
 //                per 64 handles) and four counts per tile
 //   k_tick_scan  one workgroup: the exclusive scan of the tiles' counts, the totals to pinned memory
@@ -71,6 +72,7 @@ struct TickK {
     uint64_t n;                    // handles: group records and timers
     Word *timers;
     const uint32_t *contact;       // device bitmap, bit h of word h / 32; NULL: nobody
+    const uint32_t *pending;       // the same, of hq_hb_received.hip's pending contacts; NULL: nobody
     hq_tick_params p;
     uint64_t *ballots;             // [n_tiles x kWaves x kBits]
     uint32_t *counts, *bases;      // [n_tiles x kBits]
@@ -89,7 +91,8 @@ __global__ void __launch_bounds__(kBlock) k_tick(TickK k) {
         const hq_dgroup *g = k.groups + h;
         const GroupRef r = load_group(g);
         hq_tick_timer t = unpack(k.timers[h]);
-        const bool contact = k.contact && ((k.contact[h >> 5] >> (h & 31u)) & 1u);
+        const bool contact = (k.contact && ((k.contact[h >> 5] >> (h & 31u)) & 1u)) ||
+                             (k.pending && ((k.pending[h >> 5] >> (h & 31u)) & 1u));
         const uint64_t cid = !r.suspended && tick_stale(t, r.term, r.state) ? load_cluster_id(g) : 0;
         bits = tick_step(t, k.p, cid, r.term, r.state, r.suspended, contact);
         k.timers[h] = pack(t);
@@ -172,6 +175,7 @@ struct ListedK {
     uint64_t n;
     hq_timer *pub;                 // device [n]
     uint32_t *error;               // device
+    uint32_t *pending;             // hq_hb_received.hip's pending contacts (n_state_groups bits); NULL: none
 };
 
 __global__ void __launch_bounds__(kBlock) k_tick_invalidate(ListedK k) {
@@ -191,7 +195,10 @@ __global__ void __launch_bounds__(kBlock) k_tick_get(ListedK k) {
     }
     const hq_dgroup *g = k.groups + h;
     const GroupRef r = load_group(g);
-    k.pub[i] = tick_public(unpack(k.timers[h]), k.p, load_cluster_id(g), r.term, r.state);
+    hq_timer pub = tick_public(unpack(k.timers[h]), k.p, load_cluster_id(g), r.term, r.state);
+    // (a pending contact is the next tick's leaderIsAvailable)
+    if (k.pending && ((k.pending[h >> 5] >> (h & 31u)) & 1u) && r.state != HQ_STATE_LEADER) pub.election_tick = 0;
+    k.pub[i] = pub;
 }
 
 __global__ void __launch_bounds__(kBlock) k_tick_set(ListedK k) {
@@ -205,6 +212,7 @@ __global__ void __launch_bounds__(kBlock) k_tick_set(ListedK k) {
     const hq_dgroup *g = k.groups + h;
     const GroupRef r = load_group(g);
     k.timers[h] = pack(tick_from_public(k.pub[i], k.p, load_cluster_id(g), r.term, r.state));
+    if (k.pending) atomicAnd(k.pending + (h >> 5), ~(1u << (h & 31u)));
 }
 
 template <class T>
@@ -371,7 +379,7 @@ int hq_tick_dev_invalidate(hq_tick_dev *t, uint64_t n_groups, bool all, uint64_t
 }
 
 int hq_tick_dev_run(hq_tick_dev *t, const hq_dstate_view *st, const hq_tick_params *p, bool with_contact,
-                    hq_tick_output *out) {
+                    uint32_t *pending, hq_tick_output *out) {
     hq_ctx *ctx = t->ctx;
     hipStream_t s = ctx->stream;
     const uint64_t n = st->n_groups;
@@ -396,6 +404,7 @@ int hq_tick_dev_run(hq_tick_dev *t, const hq_dstate_view *st, const hq_tick_para
     k.n = n;
     k.timers = t->timers;
     k.contact = with_contact ? t->contact : nullptr;
+    k.pending = pending;
     k.p = *p;
     k.ballots = t->ballots;
     k.counts = t->counts;
@@ -427,6 +436,8 @@ int hq_tick_dev_run(hq_tick_dev *t, const hq_dstate_view *st, const hq_tick_para
             hipLaunchKernelGGL(k_tick_emit, dim3((uint32_t)n_tiles), dim3(kBlock), 0, s, k);
             rc = hq::check_hip(ctx, hipGetLastError(), "k_tick_emit");
         }
+        // (the pending contacts are consumed)
+        if (!rc && pending) rc = hq::check_hip(ctx, hipMemsetAsync(pending, 0, cwords * 4, s), "hq_tick contacts");
         if (!rc) rc = hq::check_hip(ctx, hipEventRecord(t->ev1, s), "event");
     }
     if (queued) rc = finish(ctx, rc, "hq_worker_tick");
@@ -448,7 +459,7 @@ namespace {
 constexpr int kGet = 0, kSet = 1;
 
 int listed(hq_tick_dev *t, int direction, const hq_dstate_view *st, const hq_tick_params *p, uint64_t n,
-           const uint32_t *handles, hq_timer *host, uint32_t *error) {
+           const uint32_t *handles, hq_timer *host, uint32_t *pending, uint32_t *error) {
     hq_ctx *ctx = t->ctx;
     hipStream_t s = ctx->stream;
     const char *const what = direction == kGet ? "hq_worker_get_timers" : "hq_worker_set_timers";
@@ -469,6 +480,7 @@ int listed(hq_tick_dev *t, int direction, const hq_dstate_view *st, const hq_tic
     k.n = n;
     k.pub = t->pub;
     k.error = t->error;
+    k.pending = pending;
 
     rc = hq::check_hip(ctx, hipMemsetAsync(t->error, 0, 16, s), "memset");
     if (!rc && handles)
@@ -500,11 +512,11 @@ int listed(hq_tick_dev *t, int direction, const hq_dstate_view *st, const hq_tic
 }  // namespace
 
 int hq_tick_dev_get(hq_tick_dev *t, const hq_dstate_view *st, const hq_tick_params *p, uint64_t n,
-                    const uint32_t *handles, hq_timer *out, uint32_t *error) {
-    return listed(t, kGet, st, p, n, handles, out, error);
+                    const uint32_t *handles, hq_timer *out, uint32_t *pending, uint32_t *error) {
+    return listed(t, kGet, st, p, n, handles, out, pending, error);
 }
 
 int hq_tick_dev_set(hq_tick_dev *t, const hq_dstate_view *st, const hq_tick_params *p, uint64_t n,
-                    const uint32_t *handles, const hq_timer *timers, uint32_t *error) {
-    return listed(t, kSet, st, p, n, handles, const_cast<hq_timer *>(timers), error);
+                    const uint32_t *handles, const hq_timer *timers, uint32_t *pending, uint32_t *error) {
+    return listed(t, kSet, st, p, n, handles, const_cast<hq_timer *>(timers), pending, error);
 }

@@ -165,6 +165,7 @@ void hq_worker_close(hq_worker *w) {
     if (w->grp) hq_groups_dev_close(w->grp);
     if (w->poolc) hq_pool_dev_close(w->poolc);
     if (w->tickd) hq_tick_dev_close(w->tickd);
+    if (w->hbr) hq_hbr_dev_close(w->hbr);
     if (w->dstep) hq_dstep_close(w->dstep);
     if (w->ctx) {
         hq_sync(w->ctx);

@@ -26,17 +26,7 @@ bool is_response_type(uint32_t t) {       // isResponseMessageType (internal/raf
 
 }  // namespace
 
-void hq_worker::reset(Group &g, uint64_t term) {   // raft.reset, raft.go:991-1010
-    g.term = term;
-    g.granted = g.rejected = 0;
-    rq_release(g);
-    Member *m = members(g);
-    for (int i = 0; i < g.n_members; ++i) {          // resetRemotes/Observers/Witnesses
-        m[i].match = m[i].node_id == g.node_id ? g.last : 0;
-        m[i].active = 0;
-    }
-}
-
+// (hq_worker::reset, raft.reset: hq_worker_k.h)
 void hq_worker::become_follower(Group &g, uint64_t term, uint32_t reason) {
     g.state = HQ_STATE_FOLLOWER;                    // raft.go:949-957
     reset(g, term);

@@ -9,6 +9,7 @@
 //   hq_worker_lists.cpp  membership changes and the listed groups' fetch / resume
 //   hq_worker_lifecycle.cpp  groups started and stopped on a running worker, pool compaction
 //   hq_worker_tick.cpp   the Raft timers: one tick of every group, the listed timers' get / set
+//   hq_worker_hbrecv.cpp received heartbeats: the follower side, and the replies as wire messages
 // All of them plain C++ (no HIP headers): the worker is a client of the same ABI a cgo binding
 // would use. Every C entry's body runs inside `guarded` (hq_guard.h).
 //
@@ -27,6 +28,7 @@
 #include "hq_config.h"
 #include "hq_dstep.h"
 #include "hq_groups.h"
+#include "hq_hb_received.h"
 #include "hq_guard.h"
 #include "hq_heartbeat.h"
 #include "hq_heartbeat_wire.h"
@@ -171,6 +173,14 @@ struct hq_worker {
     std::vector<uint32_t> tk_contact, tk_lists[kTickLists];
     hq_tick_dev *tickd = nullptr;
     std::vector<uint32_t> tick_resets;
+    // received heartbeats (hq_worker_hbrecv.cpp): a host worker's output and its pending contacts
+    // (bit h of word h / 32; hr_marked: a bit may be set); a device worker's buffers and pending
+    // contacts (first call)
+    std::vector<hq_hb_reply> hr_replies;
+    std::vector<hq_hb_group_result> hr_results;
+    std::vector<uint32_t> hr_pending, hr_seen;    // (hr_seen: a call's listed handles, for its checks)
+    bool hr_marked = false;
+    hq_hbr_dev *hbr = nullptr;
     // step scratch (`touched`: the groups a call has marked kTouched, unmarked before it returns)
     const hq_step_input *in = nullptr;
     std::vector<uint32_t> work, next_work, touched;
@@ -244,7 +254,7 @@ struct hq_worker {
     inline Verdict read_index(Group &g, uint64_t from, uint64_t low, uint64_t high, uint64_t ei);
     inline void advance(Group &g);
     // reference state transitions (host bookkeeping of raft.go:949-1010)
-    inline void reset(Group &g, uint64_t term);
+    inline void reset(Group &g, uint64_t term);   // (defined below: hq_worker_hbrecv.cpp resets too)
     inline void become_follower(Group &g, uint64_t term, uint32_t reason);
     inline void become_leader(Group &g);
     void push_state(const Group &g, uint32_t reason) {
@@ -289,7 +299,24 @@ struct hq_worker {
     int tick(uint64_t n_contact, const uint32_t *contact, hq_tick_output *out);
     int get_timers(uint64_t n, const uint32_t *handles, hq_timer *out);
     int set_timers(uint64_t n, const uint32_t *handles, const hq_timer *ts);
+    // received heartbeats (hq_worker_hbrecv.cpp)
+    bool contact_pending(uint64_t h) const {
+        return hr_marked && (h >> 5) < hr_pending.size() && ((hr_pending[h >> 5] >> (h & 31u)) & 1u);
+    }
+    int clear_pending_contacts();
+    int heartbeats_received(const hq_hb_received_input *in, hq_hb_received_output *out);
 };
+
+inline void hq_worker::reset(Group &g, uint64_t term) {   // raft.reset, raft.go:991-1010
+    g.term = term;
+    g.granted = g.rejected = 0;
+    rq_release(g);
+    Member *m = members(g);
+    for (int i = 0; i < g.n_members; ++i) {          // resetRemotes/Observers/Witnesses
+        m[i].match = m[i].node_id == g.node_id ? g.last : 0;
+        m[i].active = 0;
+    }
+}
 
 // Marks each of a list's n groups kTouched while they are checked, so that a group listed twice
 // is seen, and always unmarks them (hq_worker_lists.cpp, hq_worker_lifecycle.cpp): handle_of(i, h) finds entry i's group (or fails), check(i, h)

@@ -3,7 +3,9 @@
 // timers' get / set, host and device arms. The transition is hq_tick.h's for both: a host worker
 // applies it to its own records here, a device worker's kernels (hq_tick.hip) to the resident ones.
 // None of the calls reads the device state back or touches host_stale: which handles are live is
-// the mirror's own structure, and (term, state) are read where they live.
+// the mirror's own structure, and (term, state) are read where they live. The contacts that
+// hq_worker_heartbeats_received marked since the last tick (hq_worker_hbrecv.cpp; a device worker's
+// in hq_hb_received.hip's device bitmap) are a second contact set of the tick, consumed by it.
 #include "hq_worker_k.h"
 
 using namespace hq::wk;
@@ -50,6 +52,7 @@ int hq_worker::set_tick_config(const hq_tick_config *cfg) {
         return fail(HQ_E_INVAL, "hq_worker_set_tick_config: check_quorum must be 0 or 1, reserved 0");
     tick_p = hq_tick_params{cfg->election_rtt, cfg->heartbeat_rtt, cfg->check_quorum, cfg->seed};
     tick_on = true;
+    if (int rc = clear_pending_contacts()) return rc;   // (of received heartbeats)
     // every timer reset
     if (dstep) {
         tick_reset_all = true;
@@ -79,10 +82,19 @@ int hq_worker::tick(uint64_t n_contact, const uint32_t *contact, hq_tick_output 
         hq_dstate_view st;
         hq_dstep_view(dstep, &st);
         if (st.n_groups != G) return fail(HQ_E_STATE, "hq_worker_tick: the resident state is not the host's size (internal)");
-        return hq(hq_tick_dev_run(tickd, &st, &tick_p, n_contact != 0, out), entry);
+        // the contacts hq_worker_heartbeats_received marked on the device since the last tick
+        uint32_t *pending = nullptr;
+        if (hbr && (rc = hq(hq_hbr_dev_pending(hbr, G, &pending), entry))) return rc;
+        rc = hq(hq_tick_dev_run(tickd, &st, &tick_p, n_contact != 0, pending, out), entry);
+        if (!rc && pending) hq_hbr_dev_consumed(hbr);
+        return rc;
     }
     tick_flush(entry);
     tk_contact.assign((G + 31) / 32, 0);
+    if (hr_marked) {                                // the received heartbeats' contacts, consumed
+        for (size_t i = 0; i < std::min(tk_contact.size(), hr_pending.size()); ++i) tk_contact[i] = hr_pending[i];
+        clear_pending_contacts();
+    }
     for (uint64_t i = 0; i < n_contact; ++i) tk_contact[contact[i] >> 5] |= 1u << (contact[i] & 31u);
     for (auto &l : tk_lists) l.clear();
     uint64_t ticked = 0;
@@ -106,6 +118,7 @@ int hq_worker::tick(uint64_t n_contact, const uint32_t *contact, hq_tick_output 
 
 int hq_worker::get_timers(uint64_t n, const uint32_t *handles, hq_timer *out) {
     const char *const entry = "hq_worker_get_timers";
+    const uint64_t G = groups.size();
     if (!tick_on) return fail(HQ_E_STATE, "hq_worker_get_timers: no tick config (hq_worker_set_tick_config)");
     for (uint64_t i = 0; i < n; ++i)
         if (!live(handles ? handles[i] : i)) return fail(HQ_E_INVAL, "hq_worker_get_timers: unknown group handle");
@@ -116,7 +129,9 @@ int hq_worker::get_timers(uint64_t n, const uint32_t *handles, hq_timer *out) {
         hq_dstate_view st;
         hq_dstep_view(dstep, &st);
         uint32_t e = 0;
-        rc = hq_tick_dev_get(tickd, &st, &tick_p, n, handles, out, &e);
+        uint32_t *pending = nullptr;
+        if (hbr && (rc = hq(hq_hbr_dev_pending(hbr, G, &pending), entry))) return rc;
+        rc = hq_tick_dev_get(tickd, &st, &tick_p, n, handles, out, pending, &e);
         if (rc == HQ_E_INVAL && e)
             return fail(HQ_E_STATE, "hq_worker_get_timers: a live handle beyond the resident state (internal)");
         return hq(rc, entry);
@@ -126,12 +141,14 @@ int hq_worker::get_timers(uint64_t n, const uint32_t *handles, hq_timer *out) {
         const uint64_t h = handles ? handles[i] : i;
         const Group &g = groups[h];
         out[i] = tick_public(timers[h], tick_p, g.cluster_id, g.term, g.state);
+        if (contact_pending(h) && g.state != HQ_STATE_LEADER) out[i].election_tick = 0;
     }
     return HQ_OK;
 }
 
 int hq_worker::set_timers(uint64_t n, const uint32_t *handles, const hq_timer *ts) {
     const char *const entry = "hq_worker_set_timers";
+    const uint64_t G = groups.size();
     if (!tick_on) return fail(HQ_E_STATE, "hq_worker_set_timers: no tick config (hq_worker_set_tick_config)");
     // every entry is checked before any is applied
     int rc = check_distinct(
@@ -155,7 +172,9 @@ int hq_worker::set_timers(uint64_t n, const uint32_t *handles, const hq_timer *t
         hq_dstate_view st;
         hq_dstep_view(dstep, &st);
         uint32_t e = 0;
-        rc = hq_tick_dev_set(tickd, &st, &tick_p, n, handles, ts, &e);
+        uint32_t *pending = nullptr;
+        if (hbr && (rc = hq(hq_hbr_dev_pending(hbr, G, &pending), entry))) return rc;
+        rc = hq_tick_dev_set(tickd, &st, &tick_p, n, handles, ts, pending, &e);
         if (rc == HQ_E_INVAL && e)
             return fail(HQ_E_STATE, "hq_worker_set_timers: a live handle beyond the resident state (internal)");
         return hq(rc, entry);
@@ -165,6 +184,7 @@ int hq_worker::set_timers(uint64_t n, const uint32_t *handles, const hq_timer *t
         const uint64_t h = handles ? handles[i] : i;
         const Group &g = groups[h];
         timers[h] = tick_from_public(ts[i], tick_p, g.cluster_id, g.term, g.state);
+        if (contact_pending(h)) hr_pending[h >> 5] &= ~(1u << (h & 31u));
     }
     return HQ_OK;
 }

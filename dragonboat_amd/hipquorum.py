@@ -299,6 +299,35 @@ TIMER_DTYPE = np.dtype([("election_tick", "<u4"), ("heartbeat_tick", "<u4"),
 assert (ctypes.sizeof(TickConfig), ctypes.sizeof(TickOutput), TIMER_DTYPE.itemsize) == (24, 64, 16)
 
 
+# heartbeats received (hq_worker_heartbeats_received, hq_heartbeat_replies_expand)
+HQ_MSG_NOOP = 4
+HQ_HBR_COMMITTED, HQ_HBR_COMMIT_ABOVE_LAST, HQ_HBR_CONTACT, HQ_HBR_SUSPENDED = 1, 2, 4, 8
+HB_RECEIVED_DTYPE = np.dtype([("from", "<u8"), ("term", "<u8"), ("commit", "<u8"), ("hint", "<u8"),
+                              ("hint_high", "<u8")], align=True)
+HB_REPLY_DTYPE = np.dtype([("term", "<u8"), ("type", "<u4"), ("reserved", "<u4")], align=True)
+HB_GROUP_RESULT_DTYPE = np.dtype([("term", "<u8"), ("commit", "<u8"), ("leader", "<u8"),
+                                  ("state", "<u4"), ("flags", "<u2"), ("n_resets", "<u2")], align=True)
+
+
+class HbReceivedInput(ctypes.Structure):
+    """Mirror of ``hq_hb_received_input``."""
+    _fields_ = [("n_groups", ctypes.c_uint64), ("groups", _vp), ("offsets", _vp), ("msgs", _vp),
+                ("check_quorum", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class HbReceivedOutput(ctypes.Structure):
+    """Mirror of ``hq_hb_received_output``."""
+    _fields_ = [("replies", _vp), ("n_msgs", ctypes.c_uint64), ("results", _vp),
+                ("n_groups", ctypes.c_uint64), ("n_resp", ctypes.c_uint64), ("n_noop", ctypes.c_uint64),
+                ("n_contact", ctypes.c_uint64), ("n_committed", ctypes.c_uint64),
+                ("n_state_changed", ctypes.c_uint64), ("n_suspended", ctypes.c_uint64),
+                ("gpu_ns", ctypes.c_uint64)]
+
+
+assert (HB_RECEIVED_DTYPE.itemsize, HB_REPLY_DTYPE.itemsize, HB_GROUP_RESULT_DTYPE.itemsize,
+        ctypes.sizeof(HbReceivedInput), ctypes.sizeof(HbReceivedOutput)) == (40, 16, 32, 40, 88)
+
+
 class WireBatchInfo(ctypes.Structure):
     _fields_ = [("n_messages", ctypes.c_uint64), ("deployment_id", ctypes.c_uint64),
                 ("source_address_len", ctypes.c_uint64), ("bin_ver", ctypes.c_uint32),
@@ -584,6 +613,11 @@ SIGNATURES = {
                                        ctypes.c_uint32, ctypes.c_uint32]),
     "hq_worker_get_timers": (ctypes.c_int, [_vp, ctypes.c_uint64, _vp, _vp]),
     "hq_worker_set_timers": (ctypes.c_int, [_vp, ctypes.c_uint64, _vp, _vp]),
+    "hq_worker_heartbeats_received": (ctypes.c_int, [_vp, ctypes.POINTER(HbReceivedInput),
+                                                     ctypes.POINTER(HbReceivedOutput)]),
+    "hq_heartbeat_replies_expand": (ctypes.c_int, [ctypes.POINTER(HbReceivedInput),
+                                                   ctypes.POINTER(HbReceivedOutput), _vp, _vp, _vp,
+                                                   ctypes.c_uint64, _u64p]),
     "hq_synth_commit_dev": (ctypes.c_int, [_vp, ctypes.POINTER(SynthSpec), ctypes.POINTER(CommitArgs)]),
     "hq_synth_commit_lag_dev": (ctypes.c_int, [_vp, ctypes.POINTER(SynthSpec),
                                                ctypes.POINTER(LagArgs), _vp]),
@@ -1967,6 +2001,30 @@ class Worker:
         self._check(lib.hq_worker_set_timers(self.h, n, hp, _p(timers) if n else None),
                     "hq_worker_set_timers")
 
+    def heartbeats_received(self, groups, offsets, msgs, check_quorum=True, copy=True):
+        """hq_worker_heartbeats_received: the received Heartbeats of a step interval handled by
+        their groups. groups: uint32 handles (each at most once); offsets: uint64 [n + 1]; msgs:
+        HB_RECEIVED_DTYPE, group i's at msgs[offsets[i]:offsets[i + 1]] in arrival order. Returns
+        a dict: 'replies' (HB_REPLY_DTYPE, one per message), 'results' (HB_GROUP_RESULT_DTYPE,
+        one per listed group), the counts 'n_resp', 'n_noop', 'n_contact', 'n_committed',
+        'n_state_changed', 'n_suspended', and 'gpu_ns'. The groups in contact are marked for the
+        next tick() inside the worker. With copy=False the arrays are views of the worker's
+        buffers, valid until its next heartbeats_received."""
+        inp, _keep = hb_received_input(groups, offsets, msgs, check_quorum)
+        out = HbReceivedOutput()
+        self._check(lib.hq_worker_heartbeats_received(self.h, ctypes.byref(inp), ctypes.byref(out)),
+                    "hq_worker_heartbeats_received")
+        res = {name: int(getattr(out, name)) for name in
+               ("n_resp", "n_noop", "n_contact", "n_committed", "n_state_changed", "n_suspended", "gpu_ns")}
+        for name, ptr, count, dt in (("replies", out.replies, out.n_msgs, HB_REPLY_DTYPE),
+                                     ("results", out.results, out.n_groups, HB_GROUP_RESULT_DTYPE)):
+            if count == 0:
+                res[name] = np.zeros(0, dt)
+                continue
+            buf = (ctypes.c_char * (count * dt.itemsize)).from_address(ptr)
+            res[name] = np.frombuffer(buf, dt).copy() if copy else np.frombuffer(buf, dt)
+        return res
+
     def readback_count(self) -> int:
         """hq_worker_readback_count: how often the device-resident state was copied back."""
         n = ctypes.c_uint64(0)
@@ -2405,6 +2463,42 @@ def heartbeats_expand(hb, cluster_id, term, committed, n_members, member_ids, ca
         e.n = n.value
         raise e
     return msgs[:n.value]
+
+
+def hb_received_input(groups, offsets, msgs, check_quorum=True):
+    """An HbReceivedInput over the given arrays, and the arrays it points into (keep them alive)."""
+    g = np.ascontiguousarray(groups, np.uint32)
+    o = np.ascontiguousarray(offsets, np.uint64)
+    m = np.ascontiguousarray(msgs, HB_RECEIVED_DTYPE)
+    assert len(o) == len(g) + 1
+    inp = HbReceivedInput(len(g), _p(g) if len(g) else None, _p(o), _p(m) if len(m) else None,
+                          int(check_quorum), 0)
+    return inp, (g, o, m)
+
+
+def heartbeat_replies_expand(groups, offsets, msgs, res, cluster_id, node_id, cap=None):
+    """hq_heartbeat_replies_expand: the replies of Worker.heartbeats_received (`res`, or a dict
+    built by hand with 'replies' and 'results') as WIRE_MESSAGE_DTYPE rows for encode_wire_batch;
+    cluster_id / node_id per listed group. cap: the message buffer's size (None: one per input
+    message); a short one raises HQError(HQ_E_STATE) whose `.n` is the count needed."""
+    inp, _keep = hb_received_input(groups, offsets, msgs)
+    rep = np.ascontiguousarray(res["replies"], HB_REPLY_DTYPE)
+    rs = np.ascontiguousarray(res["results"], HB_GROUP_RESULT_DTYPE)
+    cid = np.ascontiguousarray(cluster_id, np.uint64)
+    nid = np.ascontiguousarray(node_id, np.uint64)
+    assert len(cid) == inp.n_groups and len(nid) == inp.n_groups
+    out = HbReceivedOutput(_p(rep) if len(rep) else None, len(rep), _p(rs) if len(rs) else None, len(rs))
+    cap = len(rep) if cap is None else cap
+    wire = np.zeros(max(cap, 1), WIRE_MESSAGE_DTYPE)
+    n = ctypes.c_uint64(0)
+    rc = lib.hq_heartbeat_replies_expand(ctypes.byref(inp), ctypes.byref(out), _p(cid) if len(cid) else None,
+                                         _p(nid) if len(nid) else None, _p(wire), cap, ctypes.byref(n))
+    if rc != HQ_OK:
+        e = HQError(rc, "hq_heartbeat_replies_expand: " + ("the replies do not fit cap" if rc == HQ_E_STATE
+                                                           else "inconsistent input"))
+        e.n = n.value
+        raise e
+    return wire[:n.value]
 
 
 def heartbeat_wire_messages(msgs, frm):

@@ -1918,6 +1918,115 @@ int hq_tick_timeout(uint64_t seed, uint64_t cluster_id, uint64_t term, uint32_t 
 int hq_worker_get_timers(hq_worker *w, uint64_t n, const uint32_t *handles, hq_timer *out);
 int hq_worker_set_timers(hq_worker *w, uint64_t n, const uint32_t *handles, const hq_timer *timers);
 
+/* ---------------------------------------------------------------- heartbeats received ------- */
+/*
+ * The follower side of heartbeats: a step interval's received Heartbeats (type 17) handled where
+ * the group state lives, next to the step, for host and device workers alike. Per listed group the
+ * call gives what the reference gives when it handles exactly these messages, in this order,
+ * through Peer.Handle in the group's state at the call (Peer.Handle passes a Heartbeat from any
+ * sender: it is not a response type, peer.go:191-197). It returns one reply per message and one
+ * result per group, and marks the groups that heard from their leader for the next hq_worker_tick
+ * (on the device for a device worker: the contacts never pass through the host, and the caller's
+ * `contact` list carries only what Replicate caused). A device worker's kernel is
+ * hq_hb_received.hip's; nothing is read back: hq_worker_readback_count moves in none of these
+ * calls. Additions to ABI 21 (new symbols only). The step keeps its behaviour: a type 17 inside a
+ * step is still an unknown type there and suspends its group.
+ *
+ * A suspended group (a vacant handle's tombstone included) handles no message: every reply of it
+ * has type 0, its result's flags are HQ_HBR_SUSPENDED, its term and state are the record's, and
+ * nothing is written. Otherwise, per message, in this order (term, state, committed, last_index
+ * are the group's resident ones):
+ *   1. m.term != 0 && m.term > term: becomeFollower(m.term, m.from) (onMessageTermNotMatched,
+ *      raft.go:1425-1438; raft.go:949-957): state follower and reset(m.term) exactly as the
+ *      step's reset (raft.go:991-1010): votes cleared, pending reads dropped, every member's match
+ *      0 but the node's own at last_index, active flags cleared; n_resets++. Processing goes on at
+ *      3 as a follower.
+ *   2. m.term != 0 && m.term < term: the reply is a NoOP with the group's term when check_quorum
+ *      is set (raft.go:1439-1444), else none. Nothing else happens: no contact.
+ *   3. The term matched (or is 0).
+ *      A leader has no handler (raft.go:2043-2057 registers none): no reply.
+ *      A candidate runs becomeFollower(term, m.from) (handleCandidateHeartbeat, raft.go:1963-1966),
+ *      n_resets++, and goes on as a follower.
+ *      A follower (handleFollowerHeartbeat, raft.go:1869-1873): contact (leaderIsAvailable,
+ *      raft.go:1859-1861; HQ_HBR_CONTACT) and leader = m.from (setLeaderID); commitTo(m.commit)
+ *      (handleHeartbeatMessage, raft.go:1302-1310): when committed < m.commit <= last_index the
+ *      resident committed = m.commit (HQ_HBR_COMMITTED); when m.commit > last_index the record is
+ *      left as it is and HQ_HBR_COMMIT_ABOVE_LAST is set; result.commit = max(result.commit,
+ *      m.commit). The host's log is the authority: a follower's resident last_index is only as
+ *      fresh as its last sync (Replicate stays on the CPU), and the host applies commitTo from
+ *      the result's column. The reply is a HeartbeatResp with the group's term.
+ * A reply of type 0 has term 0. n_resp / n_noop count the replies by type; n_contact, n_committed
+ * and n_suspended the groups with that flag; n_state_changed the groups with n_resets > 0.
+ *
+ * Contact is recorded per handle in the worker and applied by the next hq_worker_tick exactly like
+ * a handle of its `contact` list, then cleared; it composes with that list. hq_worker_get_timers
+ * returns a non-leader with a pending contact with election_tick 0, hq_worker_set_timers clears
+ * its handles' pending contacts, hq_worker_set_tick_config clears them all. The call works before
+ * a tick config is set. A state change needs no signal to the timers: the tick observes the
+ * (term, state) pair.
+ *
+ * HQ_E_INVAL, with hq_worker_last_error set and nothing handled, written or marked: a NULL w, in
+ * or out; check_quorum above 1 or reserved nonzero; n_groups >= 2^28 or offsets[n_groups] >= 2^31;
+ * NULL groups or offsets with n_groups > 0, NULL msgs with messages; offsets that decrease or do
+ * not start at 0; a handle at or beyond the group count, or listed twice. n_groups = 0 is HQ_OK
+ * with empty outputs. The output arrays are the worker's own (pinned for a device worker), valid
+ * until its next hq_worker_heartbeats_received or close; they are not the step's, the heartbeats'
+ * or the tick's buffers. A device worker first uploads pending hq_worker_add_group / _set_group
+ * changes, as a step does.
+ *
+ * hq_heartbeat_replies_expand is stateless and host only: the replies with type != 0, in input
+ * order, as hq_wire_messages that hq_wire_encode_batch marshals: Type, To = the message's from,
+ * From = node_id[i] and ClusterId = cluster_id[i] of the listed group i, Term = the reply's term,
+ * Hint / HintHigh echoed for a HeartbeatResp and 0 for a NoOP, everything else 0. *n is always
+ * set (0 on HQ_E_INVAL); HQ_E_STATE with nothing written when the replies do not fit cap.
+ *
+ * The caller's order: a node's queue is still split at the first message that goes elsewhere; a
+ * follower's Heartbeats that lead its queue go to this call before the step; a Heartbeat behind a
+ * message the step takes stays with the CPU.
+ *
+ * Not covered: the replies as MessageBatch bytes on the device, type 17 inside the step's own
+ * event order, Replicate / InstallSnapshot / TimeoutNow, leaderID as resident state, a node that
+ * is itself an observer or witness (the worker's node_id is always one of the remotes).
+ */
+#define HQ_MSG_NOOP 4u                      /* raft.proto:31 */
+typedef struct hq_hb_received {             /* the fields of a received Heartbeat the path reads */
+    uint64_t from, term, commit, hint, hint_high;
+} hq_hb_received;                           /* 40 bytes */
+typedef struct hq_hb_received_input {       /* rows, as hq_step_input */
+    uint64_t n_groups;
+    const uint32_t *groups;                 /* handles, each at most once */
+    const uint64_t *offsets;                /* [n_groups + 1], non-decreasing, offsets[0] = 0 */
+    const hq_hb_received *msgs;             /* group i's: msgs[offsets[i] .. offsets[i+1]), arrival order */
+    uint32_t check_quorum;                  /* 0 or 1: r.checkQuorum */
+    uint32_t reserved;                      /* 0 */
+} hq_hb_received_input;
+typedef struct hq_hb_reply {                /* one per input message, at the message's index */
+    uint64_t term;                          /* the group's term when it replied */
+    uint32_t type;                          /* 0 none, HQ_MSG_HEARTBEAT_RESP, HQ_MSG_NOOP */
+    uint32_t reserved;
+} hq_hb_reply;                              /* 16 bytes */
+typedef struct hq_hb_group_result {         /* one per listed group, input order */
+    uint64_t term;                          /* after the call */
+    uint64_t commit;                        /* largest Commit of its accepted heartbeats, 0: none */
+    uint64_t leader;                        /* From of its last accepted heartbeat (setLeaderID), 0: none */
+    uint32_t state;                         /* after the call */
+    uint16_t flags, n_resets;               /* n_resets: becomeFollower calls */
+} hq_hb_group_result;                       /* 32 bytes */
+#define HQ_HBR_COMMITTED         1u   /* the resident committed index advanced */
+#define HQ_HBR_COMMIT_ABOVE_LAST 2u   /* an accepted Commit above the resident last_index */
+#define HQ_HBR_CONTACT           4u   /* leaderIsAvailable ran: marked for the next tick */
+#define HQ_HBR_SUSPENDED         8u   /* nothing handled: the group's messages go to the CPU raft */
+typedef struct hq_hb_received_output {
+    const hq_hb_reply *replies;        uint64_t n_msgs;
+    const hq_hb_group_result *results; uint64_t n_groups;
+    uint64_t n_resp, n_noop, n_contact, n_committed, n_state_changed, n_suspended;
+    uint64_t gpu_ns;                   /* device workers: HIP-event time of the call's kernels, else 0 */
+} hq_hb_received_output;
+int hq_worker_heartbeats_received(hq_worker *w, const hq_hb_received_input *in, hq_hb_received_output *out);
+int hq_heartbeat_replies_expand(const hq_hb_received_input *in, const hq_hb_received_output *out,
+                                const uint64_t *cluster_id, const uint64_t *node_id,  /* per listed group */
+                                hq_wire_message *msgs, uint64_t cap, uint64_t *n);
+
 /* ---------------------------------------------------------------- synthetic inputs ---------- */
 
 /*

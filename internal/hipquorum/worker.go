@@ -356,6 +356,100 @@ func (x *Worker) SetTimers(handles []uint32, timers []Timer) error {
 	return nil
 }
 
+// ReceivedHeartbeat is hq_hb_received: the fields of a received Heartbeat (type 17) the follower
+// path reads. HeartbeatReply is hq_hb_reply (one per message: type 0, HQ_MSG_HEARTBEAT_RESP or
+// HQ_MSG_NOOP), HeartbeatResult hq_hb_group_result (one per listed group), WireMessage
+// hq_wire_message.
+type ReceivedHeartbeat = C.hq_hb_received
+type HeartbeatReply = C.hq_hb_reply
+type HeartbeatResult = C.hq_hb_group_result
+type WireMessage = C.hq_wire_message
+
+// ReceivedOutput is what a step interval's received Heartbeats did (hq_worker_heartbeats_received):
+// the replies at their messages' indexes and the per-group results in input order, in the
+// worker's buffers (pinned host memory on a device worker), valid until its next
+// HeartbeatsReceived.
+type ReceivedOutput struct {
+	c C.hq_hb_received_output
+}
+
+func (o *ReceivedOutput) Replies() []HeartbeatReply {
+	if o.c.n_msgs == 0 {
+		return nil
+	}
+	return unsafe.Slice((*HeartbeatReply)(unsafe.Pointer(o.c.replies)), int(o.c.n_msgs))
+}
+
+func (o *ReceivedOutput) Results() []HeartbeatResult {
+	if o.c.n_groups == 0 {
+		return nil
+	}
+	return unsafe.Slice((*HeartbeatResult)(unsafe.Pointer(o.c.results)), int(o.c.n_groups))
+}
+
+// Resps and NoOPs count the replies by type; Contacts, Committed, StateChanged and Suspended the
+// groups with HQ_HBR_CONTACT, HQ_HBR_COMMITTED, a becomeFollower and HQ_HBR_SUSPENDED.
+func (o *ReceivedOutput) Resps() uint64        { return uint64(o.c.n_resp) }
+func (o *ReceivedOutput) NoOPs() uint64        { return uint64(o.c.n_noop) }
+func (o *ReceivedOutput) Contacts() uint64     { return uint64(o.c.n_contact) }
+func (o *ReceivedOutput) Committed() uint64    { return uint64(o.c.n_committed) }
+func (o *ReceivedOutput) StateChanged() uint64 { return uint64(o.c.n_state_changed) }
+func (o *ReceivedOutput) Suspended() uint64    { return uint64(o.c.n_suspended) }
+func (o *ReceivedOutput) GPUNanos() uint64     { return uint64(o.c.gpu_ns) }
+
+// HeartbeatsReceived handles the Heartbeats that lead the queues of the listed groups (each handle
+// at most once; group i's messages are msgs[offsets[i]:offsets[i+1]] in arrival order) where the
+// state lives, as Peer.Handle would (raft.go:1416-1452, 1869-1873, 1963-1966, 1302-1310), before
+// the interval's step. The groups that heard from their leader are marked for the next Tick inside
+// the worker: its contact list carries only what Replicate caused. The caller applies commitTo
+// from the results' commit column to its own log and sends the replies (ExpandHeartbeatReplies).
+// A group whose result carries HQ_HBR_SUSPENDED handled nothing: its messages go to the CPU raft.
+func (x *Worker) HeartbeatsReceived(groups []uint32, offsets []uint64, msgs []ReceivedHeartbeat,
+	checkQuorum bool) (*ReceivedOutput, error) {
+	if len(offsets) != len(groups)+1 {
+		return nil, fmt.Errorf("hipquorum: %d offsets for %d groups", len(offsets), len(groups))
+	}
+	in := C.hq_hb_received_input{n_groups: C.uint64_t(len(groups)),
+		offsets: (*C.uint64_t)(unsafe.Pointer(&offsets[0]))}
+	if len(groups) > 0 {
+		in.groups = (*C.uint32_t)(unsafe.Pointer(&groups[0]))
+	}
+	if len(msgs) > 0 {
+		in.msgs = &msgs[0]
+	}
+	if checkQuorum {
+		in.check_quorum = 1
+	}
+	o := &ReceivedOutput{}
+	if rc := C.hq_worker_heartbeats_received(x.w, &in, &o.c); rc != C.HQ_OK {
+		return nil, x.err(rc)
+	}
+	return o, nil
+}
+
+// ExpandHeartbeatReplies writes the replies of o (the output of HeartbeatsReceived over the same
+// groups, offsets and msgs) with a type as wire messages for the batch encoder, in input order;
+// clusterIDs and nodeIDs are per listed group. Stateless (hq_heartbeat_replies_expand).
+func ExpandHeartbeatReplies(groups []uint32, offsets []uint64, msgs []ReceivedHeartbeat, o *ReceivedOutput,
+	clusterIDs, nodeIDs []uint64) ([]WireMessage, error) {
+	if len(offsets) != len(groups)+1 || len(clusterIDs) != len(groups) || len(nodeIDs) != len(groups) {
+		return nil, fmt.Errorf("hipquorum: columns do not match %d groups", len(groups))
+	}
+	if len(groups) == 0 || len(msgs) == 0 {
+		return nil, nil
+	}
+	in := C.hq_hb_received_input{n_groups: C.uint64_t(len(groups)),
+		groups: (*C.uint32_t)(unsafe.Pointer(&groups[0])), offsets: (*C.uint64_t)(unsafe.Pointer(&offsets[0])),
+		msgs: &msgs[0]}
+	out := make([]WireMessage, len(msgs))
+	var n C.uint64_t
+	if rc := C.hq_heartbeat_replies_expand(&in, &o.c, (*C.uint64_t)(unsafe.Pointer(&clusterIDs[0])),
+		(*C.uint64_t)(unsafe.Pointer(&nodeIDs[0])), &out[0], C.uint64_t(len(out)), &n); rc != C.HQ_OK {
+		return nil, fmt.Errorf("hipquorum: hq_heartbeat_replies_expand: %d", int(rc))
+	}
+	return out[:n], nil
+}
+
 // Output is one step's results; the lists live in the worker's pinned buffers and are valid
 // until the worker's next step.
 type Output struct {
