@@ -15,10 +15,9 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <new>
 
 #include "hq_config.h"
-#include "hq_internal.h"
+#include "hq_sidecar.h"
 
 namespace {
 
@@ -251,79 +250,18 @@ __global__ void __launch_bounds__(kBlock) k_cfg_apply(CfgK k) {
     k.committed[i] = commit;
 }
 
-template <class T>
-int grow_dev(hq_ctx *ctx, T **p, size_t *cap, size_t need, const char *what) {
-    if (need <= *cap) return HQ_OK;
-    const size_t want = need + need / 2;
-    T *n = nullptr;
-    int rc = hq::check_hip(ctx, hipMalloc(reinterpret_cast<void **>(&n), want * sizeof(T)), what);
-    if (rc) return rc;
-    if (*p) (void)hipFree(*p);
-    *p = n;
-    *cap = want;
-    return HQ_OK;
-}
-
-template <class T>
-int grow_pinned(hq_ctx *ctx, T **p, size_t *cap, size_t need, const char *what) {
-    if (need <= *cap) return HQ_OK;
-    const size_t want = need + need / 2;
-    T *n = nullptr;
-    int rc = hq::check_hip(ctx, hipHostMalloc(reinterpret_cast<void **>(&n), want * sizeof(T),
-                                              hipHostMallocDefault), what);
-    if (rc) return rc;
-    if (*p) (void)hipHostFree(*p);
-    *p = n;
-    *cap = want;
-    return HQ_OK;
-}
-
 }  // namespace
 
-struct hq_cfg_dev {
-    hq_ctx *ctx = nullptr;
-    hq_cfg_desc *desc = nullptr;       // device
-    hq_cfg_desc *desc_host = nullptr;  // pinned staging of the descriptors
-    uint32_t *error = nullptr;         // device
-    uint32_t *status = nullptr;        // pinned host columns
-    uint64_t *committed = nullptr;
-    uint32_t *error_host = nullptr;    // pinned
-    size_t desc_cap = 0, desc_host_cap = 0, status_cap = 0, committed_cap = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+struct hq_cfg_dev : hq::Sidecar {      // (totals: the error word as the host reads it)
+    hq::DevBuf<hq_cfg_desc> desc;      // device
+    hq::PinBuf<hq_cfg_desc> desc_host; // pinned staging of the descriptors
+    hq::PinBuf<uint32_t> status;       // pinned host columns
+    hq::PinBuf<uint64_t> committed;
 };
 
-int hq_cfg_dev_open(hq_ctx *ctx, hq_cfg_dev **out) {
-    *out = new (std::nothrow) hq_cfg_dev();
-    if (!*out) return HQ_E_NOMEM;
-    hq_cfg_dev *c = *out;
-    c->ctx = ctx;
-    int rc = hq::check_hip(ctx, hipSetDevice(ctx->device), "hipSetDevice");
-    for (hipEvent_t *e : {&c->ev0, &c->ev1})
-        if (!rc) rc = hq::check_hip(ctx, hipEventCreate(e), "event");
-    if (!rc) rc = hq::check_hip(ctx, hipMalloc(reinterpret_cast<void **>(&c->error), 16),
-                                "hq_config error word");
-    if (!rc)
-        rc = hq::check_hip(ctx, hipHostMalloc(reinterpret_cast<void **>(&c->error_host), 64,
-                                              hipHostMallocDefault), "hq_config error word");
-    if (rc) {
-        hq_cfg_dev_close(c);
-        *out = nullptr;
-    }
-    return rc;
-}
+int hq_cfg_dev_open(hq_ctx *ctx, hq_cfg_dev **out) { return hq::sidecar_open(ctx, out, "hq_config error word"); }
 
-void hq_cfg_dev_close(hq_cfg_dev *c) {
-    if (!c) return;
-    (void)hipSetDevice(c->ctx->device);
-    (void)hipStreamSynchronize(c->ctx->stream);
-    for (void *p : {(void *)c->desc, (void *)c->error})
-        if (p) (void)hipFree(p);
-    for (void *p : {(void *)c->desc_host, (void *)c->status, (void *)c->committed, (void *)c->error_host})
-        if (p) (void)hipHostFree(p);
-    for (hipEvent_t e : {c->ev0, c->ev1})
-        if (e) (void)hipEventDestroy(e);
-    delete c;
-}
+void hq_cfg_dev_close(hq_cfg_dev *c) { hq::sidecar_close(c); }
 
 int hq_cfg_dev_run(hq_cfg_dev *c, const hq_dstate_mut *st, uint64_t n_member_records, uint64_t n,
                    const hq_cfg_desc *desc, const uint32_t **status, const uint64_t **committed,
@@ -333,12 +271,12 @@ int hq_cfg_dev_run(hq_cfg_dev *c, const hq_dstate_mut *st, uint64_t n_member_rec
     *error = 0;
     *gpu_ns = 0;
     int rc = hq::check_hip(ctx, hipSetDevice(ctx->device), "hipSetDevice");
-    if (!rc) rc = grow_dev(ctx, &c->desc, &c->desc_cap, n, "hq_config descriptors");
-    if (!rc) rc = grow_pinned(ctx, &c->desc_host, &c->desc_host_cap, n, "hq_config descriptors");
-    if (!rc) rc = grow_pinned(ctx, &c->status, &c->status_cap, n, "hq_config status");
-    if (!rc) rc = grow_pinned(ctx, &c->committed, &c->committed_cap, n, "hq_config commits");
+    if (!rc) rc = c->desc.grow(ctx, n, "hq_config descriptors");
+    if (!rc) rc = c->desc_host.grow(ctx, n, "hq_config descriptors");
+    if (!rc) rc = c->status.grow(ctx, n, "hq_config status");
+    if (!rc) rc = c->committed.grow(ctx, n, "hq_config commits");
     if (rc) return rc;
-    std::copy(desc, desc + n, c->desc_host);
+    std::copy(desc, desc + n, c->desc_host.get());
 
     CfgK k{};
     k.groups = st->groups;
@@ -350,34 +288,31 @@ int hq_cfg_dev_run(hq_cfg_dev *c, const hq_dstate_mut *st, uint64_t n_member_rec
     k.n = n;
     k.status = c->status;
     k.committed = c->committed;
-    k.error = c->error;
+    k.error = c->error();
 
+    // (from here on every return is finish's: the staging is rewritten by the next call)
     rc = hq::check_hip(ctx, hipEventRecord(c->ev0, s), "event");
-    if (!rc) rc = hq::check_hip(ctx, hipMemsetAsync(c->error, 0, 16, s), "memset");
+    if (!rc) rc = hq::check_hip(ctx, hipMemsetAsync(c->error(), 0, 16, s), "memset");
     if (!rc)
         rc = hq::check_hip(ctx, hipMemcpyAsync(c->desc, c->desc_host, n * sizeof(hq_cfg_desc),
                                                hipMemcpyHostToDevice, s), "hq_config descriptors");
-    if (rc) return rc;
-    const uint32_t grid = (uint32_t)((n + kBlock - 1) / kBlock);
-    hipLaunchKernelGGL(k_cfg_apply, dim3(grid), dim3(kBlock), 0, s, k);
-    rc = hq::check_hip(ctx, hipGetLastError(), "k_cfg_apply");
+    if (!rc) {
+        const uint32_t grid = (uint32_t)((n + kBlock - 1) / kBlock);
+        hipLaunchKernelGGL(k_cfg_apply, dim3(grid), dim3(kBlock), 0, s, k);
+        rc = hq::check_hip(ctx, hipGetLastError(), "k_cfg_apply");
+    }
     if (!rc)
-        rc = hq::check_hip(ctx, hipMemcpyAsync(c->error_host, c->error, 4, hipMemcpyDeviceToHost, s),
+        rc = hq::check_hip(ctx, hipMemcpyAsync(c->totals, c->error(), 4, hipMemcpyDeviceToHost, s),
                            "hq_config error word");
     if (!rc) rc = hq::check_hip(ctx, hipEventRecord(c->ev1, s), "event");
-    if (!rc) rc = hq::check_hip(ctx, hipStreamSynchronize(s), "hq_worker_config_changes");
+    rc = hq::finish(ctx, rc, "hq_worker_config_changes");
     if (rc) return rc;
-    if (*c->error_host) {
-        *error = *c->error_host;
+    if ((uint32_t)c->totals[0]) {
+        *error = (uint32_t)c->totals[0];
         return HQ_E_INVAL;
-    }
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, c->ev0, c->ev1) != hipSuccess) {
-        (void)hipGetLastError();
-        ms = 0.f;
     }
     *status = c->status;
     *committed = c->committed;
-    *gpu_ns = (uint64_t)((double)ms * 1e6);
+    *gpu_ns = hq::elapsed_ns(c->ev0, c->ev1);
     return HQ_OK;
 }

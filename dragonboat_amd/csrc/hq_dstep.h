@@ -29,6 +29,27 @@ struct hq_dread {                     // a pending ReadIndex (readStatus, readin
 };
 static_assert(sizeof(hq_dread) == 40, "40-byte read records");
 
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+
+// What the kernels beside the step read of a resident group record, decoded in one place: the
+// fields of its second 16 bytes (term, committed) and of its fourth (mem, the counts, state, the
+// vote bitmaps, flags, n_reads). A kernel uses what it needs; the rest costs nothing.
+struct hq_dgroup_fields {
+    uint64_t term, committed;
+    uint32_t mem, n_members, n_voting, state, granted, rejected, flags, n_reads;
+};
+__device__ __forceinline__ hq_dgroup_fields hq_dgroup_decode(uint64_t term, uint64_t committed, const uint4 &d) {
+    return hq_dgroup_fields{term, committed, d.x, d.y & 0xFFu, (d.y >> 8) & 0xFFu, (d.y >> 16) & 0xFFu,
+                            d.y >> 24, d.z & 0xFFu, (d.z >> 8) & 0xFFu, (d.z >> 16) & 0xFFu};
+}
+__device__ __forceinline__ hq_dgroup_fields hq_dgroup_load(const hq_dgroup *g) {
+    const uint4 *p = reinterpret_cast<const uint4 *>(g);
+    const uint4 b = p[1], d = p[3];                   // term, committed | mem, 8 bytes, pad1
+    return hq_dgroup_decode((uint64_t)b.x | (uint64_t)b.y << 32, (uint64_t)b.z | (uint64_t)b.w << 32, d);
+}
+#endif
+
 constexpr uint32_t kDReads = 8;       // pending ReadIndex ctxs per group
 constexpr uint32_t kDMembers = 16;    // members per group on the device path
 constexpr uint8_t kDSuspended = 1;

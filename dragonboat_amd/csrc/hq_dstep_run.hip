@@ -6,9 +6,11 @@
 #include <cstdio>
 
 #include "hq_dstep_k.h"
+#include "hq_sidecar.h"
 
 namespace {
 
+using hq::elapsed_ns;
 using hq::grow;
 using hq::now_ns;
 using hq::wait_stream;
@@ -30,16 +32,6 @@ struct Run {
     uint64_t t0 = 0, t1 = 0, t_sub = 0, gpu_ns = 0;
     int rc = HQ_OK;
 };
-
-// GPU time between two completed events (0 if it cannot be read)
-uint64_t elapsed_ns(hipEvent_t a, hipEvent_t b) {
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, a, b) != hipSuccess) {
-        (void)hipGetLastError();
-        return 0;
-    }
-    return (uint64_t)((double)ms * 1e6);
-}
 
 // A pinned output region of `want` bytes in place of d's (whose contents go), for d and the step's
 // k. The new one is had first: if it cannot be (fail_for_test: HQ_TEST_FAIL_REGROW), the old stays

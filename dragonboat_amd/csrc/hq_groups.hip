@@ -16,10 +16,8 @@
 // spinning, no LDS, no loops.
 #include <hip/hip_runtime.h>
 
-#include <new>
-
 #include "hq_groups.h"
-#include "hq_internal.h"
+#include "hq_sidecar.h"
 
 namespace {
 
@@ -123,73 +121,23 @@ __global__ void __launch_bounds__(kBlock) k_groups_scatter(GrpK k) {
     store_member_word(mu, kTeam - first_member + l, n_units, w2);
 }
 
-// exactly `need` elements of pinned host memory (rounded up to 64): a fetch of every group of a
-// large worker is hundreds of megabytes, so no headroom
-template <class T>
-int grow_pinned(hq_ctx *ctx, T **p, size_t *cap, size_t need, const char *what) {
-    if (need <= *cap) return HQ_OK;
-    const size_t want = (need + 63) / 64 * 64;
-    T *n = nullptr;
-    int rc = hq::check_hip(ctx, hipHostMalloc(reinterpret_cast<void **>(&n), want * sizeof(T),
-                                              hipHostMallocDefault), what);
-    if (rc) return rc;
-    if (*p) (void)hipHostFree(*p);
-    *p = n;
-    *cap = want;
-    return HQ_OK;
-}
-
 }  // namespace
 
-struct hq_groups_dev {
-    hq_ctx *ctx = nullptr;
-    hq_grp_record *records = nullptr;  // pinned: the gather's output, the scatter's input
-    uint32_t *handles_host = nullptr;  // pinned staging of the handles
-    uint32_t *handles = nullptr;       // device
-    uint32_t *error = nullptr;         // device
-    uint32_t *error_host = nullptr;    // pinned
-    size_t records_cap = 0, handles_host_cap = 0, handles_cap = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+struct hq_groups_dev : hq::Sidecar {   // (totals: the error word as the host reads it)
+    hq::PinBuf<hq_grp_record> records; // pinned: the gather's output, the scatter's input
+    hq::PinBuf<uint32_t> handles_host; // pinned staging of the handles
+    hq::DevBuf<uint32_t> handles;      // device, of handles_host's capacity
 };
 
-int hq_groups_dev_open(hq_ctx *ctx, hq_groups_dev **out) {
-    *out = new (std::nothrow) hq_groups_dev();
-    if (!*out) return HQ_E_NOMEM;
-    hq_groups_dev *c = *out;
-    c->ctx = ctx;
-    int rc = hq::check_hip(ctx, hipSetDevice(ctx->device), "hipSetDevice");
-    for (hipEvent_t *e : {&c->ev0, &c->ev1})
-        if (!rc) rc = hq::check_hip(ctx, hipEventCreate(e), "event");
-    if (!rc) rc = hq::check_hip(ctx, hipMalloc(reinterpret_cast<void **>(&c->error), 16),
-                                "hq_groups error word");
-    if (!rc)
-        rc = hq::check_hip(ctx, hipHostMalloc(reinterpret_cast<void **>(&c->error_host), 64,
-                                              hipHostMallocDefault), "hq_groups error word");
-    if (rc) {
-        hq_groups_dev_close(c);
-        *out = nullptr;
-    }
-    return rc;
-}
+int hq_groups_dev_open(hq_ctx *ctx, hq_groups_dev **out) { return hq::sidecar_open(ctx, out, "hq_groups error word"); }
 
-void hq_groups_dev_close(hq_groups_dev *c) {
-    if (!c) return;
-    (void)hipSetDevice(c->ctx->device);
-    (void)hipStreamSynchronize(c->ctx->stream);
-    for (void *p : {(void *)c->handles, (void *)c->error})
-        if (p) (void)hipFree(p);
-    for (void *p : {(void *)c->records, (void *)c->handles_host, (void *)c->error_host})
-        if (p) (void)hipHostFree(p);
-    for (hipEvent_t e : {c->ev0, c->ev1})
-        if (e) (void)hipEventDestroy(e);
-    delete c;
-}
+void hq_groups_dev_close(hq_groups_dev *c) { hq::sidecar_close(c); }
 
 int hq_groups_dev_stage(hq_groups_dev *c, uint64_t n, hq_grp_record **records, uint32_t **handles) {
     hq_ctx *ctx = c->ctx;
     int rc = hq::check_hip(ctx, hipSetDevice(ctx->device), "hipSetDevice");
-    if (!rc) rc = grow_pinned(ctx, &c->records, &c->records_cap, n, "hq_groups records");
-    if (!rc) rc = grow_pinned(ctx, &c->handles_host, &c->handles_host_cap, n, "hq_groups handles");
+    if (!rc) rc = c->records.grow(ctx, n, "hq_groups records", hq::Headroom::kExact64);
+    if (!rc) rc = c->handles_host.grow(ctx, n, "hq_groups handles", hq::Headroom::kExact64);
     if (rc) return rc;
     *records = c->records;
     *handles = c->handles_host;
@@ -206,20 +154,12 @@ int run(hq_groups_dev *c, int direction, const hq_dstate_mut *st, uint64_t n_mem
     hipStream_t s = ctx->stream;
     *error = 0;
     *gpu_ns = 0;
-    if (n == 0 || n > c->records_cap || n > c->handles_host_cap || (identity && direction != kGrpGather))
+    if (n == 0 || n > c->records.cap() || n > c->handles_host.cap() || (identity && direction != kGrpGather))
         return HQ_E_INVAL;
     if ((n + kGroupsPerBlock - 1) / kGroupsPerBlock > 0x7FFFFFFFull) return HQ_E_INVAL;
     int rc = hq::check_hip(ctx, hipSetDevice(ctx->device), "hipSetDevice");
-    if (!rc && !identity && n > c->handles_cap) {
-        uint32_t *p = nullptr;
-        rc = hq::check_hip(ctx, hipMalloc(reinterpret_cast<void **>(&p), c->handles_host_cap * 4),
-                           "hq_groups handles");
-        if (!rc) {
-            if (c->handles) (void)hipFree(c->handles);
-            c->handles = p;
-            c->handles_cap = c->handles_host_cap;
-        }
-    }
+    if (!rc && !identity && n > c->handles.cap())
+        rc = c->handles.reserve(ctx, c->handles_host.cap(), "hq_groups handles");
     if (rc) return rc;
 
     GrpK k{};
@@ -228,37 +168,34 @@ int run(hq_groups_dev *c, int direction, const hq_dstate_mut *st, uint64_t n_mem
     k.members = st->members;
     k.n_state_groups = st->n_groups;
     k.n_state_members = n_member_records;
-    k.handles = identity ? nullptr : c->handles;
+    k.handles = identity ? nullptr : c->handles.get();
     k.n = n;
     k.records = c->records;
-    k.error = c->error;
+    k.error = c->error();
 
+    // (from here on every return is finish's: the staging is rewritten by the next call)
     rc = hq::check_hip(ctx, hipEventRecord(c->ev0, s), "event");
-    if (!rc) rc = hq::check_hip(ctx, hipMemsetAsync(c->error, 0, 16, s), "memset");
+    if (!rc) rc = hq::check_hip(ctx, hipMemsetAsync(c->error(), 0, 16, s), "memset");
     if (!rc && !identity)
         rc = hq::check_hip(ctx, hipMemcpyAsync(c->handles, c->handles_host, n * 4, hipMemcpyHostToDevice, s),
                            "hq_groups handles");
-    if (rc) return rc;
-    const uint32_t grid = (uint32_t)((n + kGroupsPerBlock - 1) / kGroupsPerBlock);
-    if (direction == kGrpGather) hipLaunchKernelGGL(k_groups_gather, dim3(grid), dim3(kBlock), 0, s, k);
-    else hipLaunchKernelGGL(k_groups_scatter, dim3(grid), dim3(kBlock), 0, s, k);
-    rc = hq::check_hip(ctx, hipGetLastError(), direction == kGrpGather ? "k_groups_gather" : "k_groups_scatter");
+    if (!rc) {
+        const uint32_t grid = (uint32_t)((n + kGroupsPerBlock - 1) / kGroupsPerBlock);
+        if (direction == kGrpGather) hipLaunchKernelGGL(k_groups_gather, dim3(grid), dim3(kBlock), 0, s, k);
+        else hipLaunchKernelGGL(k_groups_scatter, dim3(grid), dim3(kBlock), 0, s, k);
+        rc = hq::check_hip(ctx, hipGetLastError(), direction == kGrpGather ? "k_groups_gather" : "k_groups_scatter");
+    }
     if (!rc)
-        rc = hq::check_hip(ctx, hipMemcpyAsync(c->error_host, c->error, 4, hipMemcpyDeviceToHost, s),
+        rc = hq::check_hip(ctx, hipMemcpyAsync(c->totals, c->error(), 4, hipMemcpyDeviceToHost, s),
                            "hq_groups error word");
     if (!rc) rc = hq::check_hip(ctx, hipEventRecord(c->ev1, s), "event");
-    if (!rc) rc = hq::check_hip(ctx, hipStreamSynchronize(s), "hq_groups");
+    rc = hq::finish(ctx, rc, "hq_groups");
     if (rc) return rc;
-    if (*c->error_host) {
-        *error = *c->error_host;
+    if ((uint32_t)c->totals[0]) {
+        *error = (uint32_t)c->totals[0];
         return HQ_E_INVAL;
     }
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, c->ev0, c->ev1) != hipSuccess) {
-        (void)hipGetLastError();
-        ms = 0.f;
-    }
-    *gpu_ns = (uint64_t)((double)ms * 1e6);
+    *gpu_ns = hq::elapsed_ns(c->ev0, c->ev1);
     return HQ_OK;
 }
 

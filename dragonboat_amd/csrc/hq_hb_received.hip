@@ -22,10 +22,9 @@
 
 #include <algorithm>
 #include <cstring>
-#include <new>
 
 #include "hq_hb_received.h"
-#include "hq_internal.h"
+#include "hq_sidecar.h"
 
 namespace {
 
@@ -71,8 +70,9 @@ __global__ void __launch_bounds__(kBlock) k_hb_received(RecvK k) {
             Quad *rec = reinterpret_cast<Quad *>(k.groups + h);
             const Quad b = rec[1], c = rec[2];       // term, committed | last, term_start
             const uint4 d = reinterpret_cast<const uint4 *>(rec)[3];   // mem, 8 bytes, pad1
-            const uint32_t n_members = d.y & 0xFFu, state0 = (d.y >> 16) & 0xFFu;
-            const bool suspended = (((d.z >> 8) & 0xFFu) & kDSuspended) != 0;
+            const hq_dgroup_fields f = hq_dgroup_decode(b.x, b.y, d);
+            const uint32_t n_members = f.n_members, state0 = f.state;
+            const bool suspended = (f.flags & kDSuspended) != 0;
             if (n_members > kDMembers || (uint64_t)d.x + n_members > k.n_state_members) err |= kErrRecord;
             if (!err) {
                 hq_hbr_group g{b.x, b.y, c.x, state0, false};
@@ -128,118 +128,30 @@ __global__ void __launch_bounds__(kBlock) k_hb_received(RecvK k) {
     }
 }
 
-template <class T>
-int grow_dev(hq_ctx *ctx, T **p, size_t *cap, size_t need, const char *what) {
-    if (need <= *cap) return HQ_OK;
-    const size_t want = need + need / 2;
-    T *n = nullptr;
-    int rc = hq::check_hip(ctx, hipMalloc(reinterpret_cast<void **>(&n), want * sizeof(T)), what);
-    if (rc) return rc;
-    if (*p) (void)hipFree(*p);
-    *p = n;
-    *cap = want;
-    return HQ_OK;
-}
-
-template <class T>
-int grow_pinned(hq_ctx *ctx, T **p, size_t *cap, size_t need, const char *what) {
-    if (need <= *cap) return HQ_OK;
-    const size_t want = need + need / 2;
-    T *n = nullptr;
-    int rc = hq::check_hip(ctx, hipHostMalloc(reinterpret_cast<void **>(&n), want * sizeof(T),
-                                              hipHostMallocDefault), what);
-    if (rc) return rc;
-    if (*p) (void)hipHostFree(*p);
-    *p = n;
-    *cap = want;
-    return HQ_OK;
-}
-
-// The stream waited for whatever `rc` says: nothing of a call stays queued behind its return.
-int finish(hq_ctx *ctx, int rc, const char *what) {
-    if (rc) {
-        (void)hipStreamSynchronize(ctx->stream);     // (rc's message stands)
-        return rc;
-    }
-    return hq::check_hip(ctx, hipStreamSynchronize(ctx->stream), what);
-}
-
 }  // namespace
 
-struct hq_hbr_dev {
-    hq_ctx *ctx = nullptr;
-    uint32_t *pending = nullptr;       // device bitmap: the contacts of the next tick
-    size_t pending_words = 0;          // its words, all defined (zero beyond what was marked)
+struct hq_hbr_dev : hq::Sidecar {      // (dev: the kCounts counts, then the error word; totals: the same)
+    hq::DevBuf<uint32_t> pending;      // device bitmap: the contacts of the next tick; every word
+                                       // defined (zero beyond what was marked)
     bool marked = false;               // a run may have set a bit since the last clear
-    uint32_t *handles = nullptr;       // device: a call's input
-    uint64_t *offsets = nullptr, *msgs = nullptr;
-    size_t handles_cap = 0, offsets_cap = 0, msgs_cap = 0;
-    unsigned long long *counts = nullptr;   // device [kCounts], then the error word
-    hq_hb_reply *replies = nullptr;    // pinned
-    hq_hb_group_result *results = nullptr;
-    size_t replies_cap = 0, results_cap = 0;
-    uint64_t *totals = nullptr;        // pinned: the counts and the error word
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hq::DevBuf<uint32_t> handles;      // device: a call's input
+    hq::DevBuf<uint64_t> offsets, msgs;
+    hq::PinBuf<hq_hb_reply> replies;   // pinned
+    hq::PinBuf<hq_hb_group_result> results;
 };
 
 int hq_hbr_dev_open(hq_ctx *ctx, hq_hbr_dev **out) {
-    *out = new (std::nothrow) hq_hbr_dev();
-    if (!*out) return HQ_E_NOMEM;
-    hq_hbr_dev *r = *out;
-    r->ctx = ctx;
-    int rc = hq::check_hip(ctx, hipSetDevice(ctx->device), "hipSetDevice");
-    for (hipEvent_t *e : {&r->ev0, &r->ev1})
-        if (!rc) rc = hq::check_hip(ctx, hipEventCreate(e), "event");
-    if (!rc)
-        rc = hq::check_hip(ctx, hipMalloc(reinterpret_cast<void **>(&r->counts), (kCounts + 1) * 8),
-                           "hq_hb_received counts");
-    if (!rc)
-        rc = hq::check_hip(ctx, hipHostMalloc(reinterpret_cast<void **>(&r->totals), (kCounts + 1) * 8,
-                                              hipHostMallocDefault), "hq_hb_received totals");
-    if (rc) {
-        hq_hbr_dev_close(r);
-        *out = nullptr;
-    }
-    return rc;
+    return hq::sidecar_open(ctx, out, "hq_hb_received counts", (kCounts + 1) * 8);
 }
 
-void hq_hbr_dev_close(hq_hbr_dev *r) {
-    if (!r) return;
-    (void)hipSetDevice(r->ctx->device);
-    (void)hipStreamSynchronize(r->ctx->stream);
-    for (void *p : {(void *)r->pending, (void *)r->handles, (void *)r->offsets, (void *)r->msgs, (void *)r->counts})
-        if (p) (void)hipFree(p);
-    for (void *p : {(void *)r->replies, (void *)r->results, (void *)r->totals})
-        if (p) (void)hipHostFree(p);
-    for (hipEvent_t e : {r->ev0, r->ev1})
-        if (e) (void)hipEventDestroy(e);
-    delete r;
-}
+void hq_hbr_dev_close(hq_hbr_dev *r) { hq::sidecar_close(r); }
 
 namespace {
 
 // the pending bitmap grown with the handle space: the old words copied, the new ones zero
 int grow_pending(hq_hbr_dev *r, uint64_t n_groups) {
-    hq_ctx *ctx = r->ctx;
-    const size_t words = hq::words32(n_groups);
-    if (words <= r->pending_words) return HQ_OK;
-    const size_t want = words + words / 2;
-    uint32_t *p = nullptr;
-    int rc = hq::check_hip(ctx, hipMalloc(reinterpret_cast<void **>(&p), want * 4), "hq_hb_received contacts");
-    if (rc) return rc;
-    rc = hq::check_hip(ctx, hipMemsetAsync(p, 0, want * 4, ctx->stream), "hq_hb_received contacts");
-    if (!rc && r->pending_words && r->marked)
-        rc = hq::check_hip(ctx, hipMemcpyAsync(p, r->pending, r->pending_words * 4, hipMemcpyDeviceToDevice,
-                                               ctx->stream), "hq_hb_received contacts");
-    rc = finish(ctx, rc, "hq_hb_received contacts");   // (the copy is waited for before the old one goes)
-    if (rc) {
-        (void)hipFree(p);
-        return rc;
-    }
-    if (r->pending) (void)hipFree(r->pending);
-    r->pending = p;
-    r->pending_words = want;
-    return HQ_OK;
+    return r->pending.grow_keep(r->ctx, hq::words32(n_groups), r->marked ? r->pending.cap() : 0, 0,
+                                "hq_hb_received contacts");
 }
 
 }  // namespace
@@ -255,11 +167,11 @@ int hq_hbr_dev_run(hq_hbr_dev *r, const hq_dstate_mut *st, uint64_t n_member_rec
     if (n_msgs >= (1ull << 31)) return HQ_E_INVAL;
     int rc = hq::check_hip(ctx, hipSetDevice(ctx->device), "hipSetDevice");
     if (!rc) rc = grow_pending(r, st->n_groups);
-    if (!rc) rc = grow_dev(ctx, &r->handles, &r->handles_cap, n, what);
-    if (!rc) rc = grow_dev(ctx, &r->offsets, &r->offsets_cap, n + 1, what);
-    if (!rc) rc = grow_dev(ctx, &r->msgs, &r->msgs_cap, std::max<uint64_t>(n_msgs, 1) * 5, what);
-    if (!rc) rc = grow_pinned(ctx, &r->replies, &r->replies_cap, std::max<uint64_t>(n_msgs, 1), what);
-    if (!rc) rc = grow_pinned(ctx, &r->results, &r->results_cap, n, what);
+    if (!rc) rc = r->handles.grow(ctx, n, what);
+    if (!rc) rc = r->offsets.grow(ctx, n + 1, what);
+    if (!rc) rc = r->msgs.grow(ctx, std::max<uint64_t>(n_msgs, 1) * 5, what);
+    if (!rc) rc = r->replies.grow(ctx, std::max<uint64_t>(n_msgs, 1), what);
+    if (!rc) rc = r->results.grow(ctx, n, what);
     if (rc) return rc;
 
     RecvK k{};
@@ -273,13 +185,13 @@ int hq_hbr_dev_run(hq_hbr_dev *r, const hq_dstate_mut *st, uint64_t n_member_rec
     k.n = n;
     k.n_msgs = n_msgs;
     k.check_quorum = in->check_quorum;
-    k.replies = reinterpret_cast<Quad *>(r->replies);
-    k.results = reinterpret_cast<Quad *>(r->results);
+    k.replies = reinterpret_cast<Quad *>(r->replies.get());
+    k.results = reinterpret_cast<Quad *>(r->results.get());
     k.pending = r->pending;
-    k.counts = r->counts;
-    k.error = reinterpret_cast<uint32_t *>(r->counts + kCounts);
+    k.counts = reinterpret_cast<unsigned long long *>(r->dev.get());
+    k.error = reinterpret_cast<uint32_t *>(r->dev + kCounts);
 
-    rc = hq::check_hip(ctx, hipMemsetAsync(r->counts, 0, (kCounts + 1) * 8, s), what);
+    rc = hq::check_hip(ctx, hipMemsetAsync(r->dev, 0, (kCounts + 1) * 8, s), what);
     if (!rc) rc = hq::check_hip(ctx, hipMemcpyAsync(r->handles, in->groups, n * 4, hipMemcpyHostToDevice, s), what);
     if (!rc)
         rc = hq::check_hip(ctx, hipMemcpyAsync(r->offsets, in->offsets, (n + 1) * 8, hipMemcpyHostToDevice, s), what);
@@ -294,10 +206,10 @@ int hq_hbr_dev_run(hq_hbr_dev *r, const hq_dstate_mut *st, uint64_t n_member_rec
         rc = hq::check_hip(ctx, hipGetLastError(), "k_hb_received");
     }
     if (!rc)
-        rc = hq::check_hip(ctx, hipMemcpyAsync(r->totals, r->counts, (kCounts + 1) * 8, hipMemcpyDeviceToHost, s),
+        rc = hq::check_hip(ctx, hipMemcpyAsync(r->totals, r->dev, (kCounts + 1) * 8, hipMemcpyDeviceToHost, s),
                            what);
     if (!rc) rc = hq::check_hip(ctx, hipEventRecord(r->ev1, s), "event");
-    rc = finish(ctx, rc, what);
+    rc = hq::finish(ctx, rc, what);
     if (rc) return rc;
     if ((uint32_t)r->totals[kCounts])
         return hq::fail(ctx, HQ_E_STATE, "hq_hb_received: a listed handle, its offsets or its resident record "
@@ -312,12 +224,7 @@ int hq_hbr_dev_run(hq_hbr_dev *r, const hq_dstate_mut *st, uint64_t n_member_rec
     out->n_committed = r->totals[3];
     out->n_state_changed = r->totals[4];
     out->n_suspended = r->totals[5];
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, r->ev0, r->ev1) != hipSuccess) {
-        (void)hipGetLastError();
-        ms = 0.f;
-    }
-    out->gpu_ns = (uint64_t)((double)ms * 1e6);
+    out->gpu_ns = hq::elapsed_ns(r->ev0, r->ev1);
     return HQ_OK;
 }
 
@@ -337,9 +244,9 @@ int hq_hbr_dev_clear(hq_hbr_dev *r) {
     hq_ctx *ctx = r->ctx;
     int rc = hq::check_hip(ctx, hipSetDevice(ctx->device), "hipSetDevice");
     if (!rc)
-        rc = hq::check_hip(ctx, hipMemsetAsync(r->pending, 0, r->pending_words * 4, ctx->stream),
+        rc = hq::check_hip(ctx, hipMemsetAsync(r->pending, 0, r->pending.cap() * 4, ctx->stream),
                            "hq_hb_received contacts");
-    rc = finish(ctx, rc, "hq_hb_received contacts");
+    rc = hq::finish(ctx, rc, "hq_hb_received contacts");
     if (!rc) r->marked = false;
     return rc;
 }

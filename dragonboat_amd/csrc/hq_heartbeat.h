@@ -57,7 +57,7 @@ __device__ inline MemberRef load_member(const hq_dmember *m) {
     return MemberRef{p[1], (uint32_t)(tail >> 16) & 0xFFu};
 }
 
-// the group's fields of the broadcast from its second and fourth 16 bytes
+// the group's fields of the broadcast (hq_dgroup_load, hq_dstep.h)
 struct GroupRef {
     uint64_t term, committed;
     uint32_t mem, n_members, n_voting, n_reads;
@@ -65,18 +65,9 @@ struct GroupRef {
 };
 
 __device__ inline GroupRef load_group(const hq_dgroup *g) {
-    const uint4 *p = reinterpret_cast<const uint4 *>(g);
-    const uint4 b = p[1], d = p[3];                   // term, committed | mem, 8 bytes, pad1
-    GroupRef r;
-    r.term = (uint64_t)b.x | (uint64_t)b.y << 32;
-    r.committed = (uint64_t)b.z | (uint64_t)b.w << 32;
-    r.mem = d.x;
-    r.n_members = d.y & 0xFFu;
-    r.n_voting = (d.y >> 8) & 0xFFu;
-    const uint32_t state = (d.y >> 16) & 0xFFu, flags = (d.z >> 8) & 0xFFu;
-    r.n_reads = (d.z >> 16) & 0xFFu;
-    r.sends = state == HQ_STATE_LEADER && !(flags & kDSuspended);
-    return r;
+    const hq_dgroup_fields f = hq_dgroup_load(g);
+    return GroupRef{f.term, f.committed, f.mem, f.n_members, f.n_voting, f.n_reads,
+                    f.state == HQ_STATE_LEADER && !(f.flags & kDSuspended)};
 }
 
 // the record checks the kernels rely on (the worker's own uploads satisfy them); a record without

@@ -20,10 +20,9 @@
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
-#include <new>
 
 #include "hq_heartbeat.h"
-#include "hq_internal.h"
+#include "hq_sidecar.h"
 
 namespace {
 
@@ -136,116 +135,50 @@ __global__ void __launch_bounds__(kBlock) k_hb_records(HbK k) {
 
 }  // namespace
 
-struct hq_hb_dev {
-    hq_ctx *ctx = nullptr;
-    uint32_t *list = nullptr;      // device copies / columns, grown on demand
-    uint64_t *meta = nullptr, *scan = nullptr;
-    uint64_t *misc = nullptr;      // the error word (its low half), the messages' sum
-    void *scan_tmp = nullptr;
-    size_t list_cap = 0, meta_cap = 0, scan_cap = 0, scan_tmp_cap = 0;   // (items; bytes)
-    uint32_t *words = nullptr;     // pinned host
-    hq_heartbeat_lag *lags = nullptr;
-    hq_heartbeat_ctx *ctxs = nullptr;
-    uint64_t *totals = nullptr;
-    size_t words_cap = 0, lag_cap = 0, ctx_cap = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+struct hq_hb_dev : hq::Sidecar {       // (dev: the error word in its low half, the messages' sum)
+    hq::DevBuf<uint32_t> list;         // device copies / columns, grown on demand
+    hq::DevBuf<uint64_t> meta, scan;
+    hq::DevBuf<uint8_t> scan_tmp;      // hipcub's temporary
+    hq::PinBuf<uint32_t> words;        // pinned host
+    hq::PinBuf<hq_heartbeat_lag> lags;
+    hq::PinBuf<hq_heartbeat_ctx> ctxs;
 };
 
-namespace {
+int hq_hb_dev_open(hq_ctx *ctx, hq_hb_dev **out) { return hq::sidecar_open(ctx, out, "hq_heartbeat"); }
 
-template <class T>
-int grow_dev(hq_ctx *ctx, T **p, size_t *cap, size_t need, const char *what) {
-    if (need <= *cap) return HQ_OK;
-    const size_t want = need + need / 2;
-    T *n = nullptr;
-    int rc = hq::check_hip(ctx, hipMalloc(reinterpret_cast<void **>(&n), want * sizeof(T)), what);
-    if (rc) return rc;
-    if (*p) (void)hipFree(*p);
-    *p = n;
-    *cap = want;
-    return HQ_OK;
-}
-
-template <class T>
-int grow_pinned(hq_ctx *ctx, T **p, size_t *cap, size_t need, const char *what) {
-    if (need <= *cap) return HQ_OK;
-    const size_t want = need + need / 2;
-    T *n = nullptr;
-    int rc = hq::check_hip(ctx, hipHostMalloc(reinterpret_cast<void **>(&n), want * sizeof(T),
-                                              hipHostMallocDefault), what);
-    if (rc) return rc;
-    if (*p) (void)hipHostFree(*p);
-    *p = n;
-    *cap = want;
-    return HQ_OK;
-}
-
-}  // namespace
-
-int hq_hb_dev_open(hq_ctx *ctx, hq_hb_dev **out) {
-    *out = new (std::nothrow) hq_hb_dev();
-    if (!*out) return HQ_E_NOMEM;
-    hq_hb_dev *h = *out;
-    h->ctx = ctx;
-    int rc = hq::check_hip(ctx, hipSetDevice(ctx->device), "hipSetDevice");
-    for (hipEvent_t *e : {&h->ev0, &h->ev1})
-        if (!rc) rc = hq::check_hip(ctx, hipEventCreate(e), "event");
-    if (!rc) rc = hq::check_hip(ctx, hipMalloc(reinterpret_cast<void **>(&h->misc), 16),
-                                "hq_heartbeat error word");
-    if (!rc)
-        rc = hq::check_hip(ctx, hipHostMalloc(reinterpret_cast<void **>(&h->totals), 64,
-                                              hipHostMallocDefault), "hq_heartbeat totals");
-    if (rc) {
-        hq_hb_dev_close(h);
-        *out = nullptr;
-    }
-    return rc;
-}
-
-void hq_hb_dev_close(hq_hb_dev *h) {
-    if (!h) return;
-    (void)hipSetDevice(h->ctx->device);
-    (void)hipStreamSynchronize(h->ctx->stream);
-    for (void *p : {(void *)h->list, (void *)h->meta, (void *)h->scan, (void *)h->misc, h->scan_tmp})
-        if (p) (void)hipFree(p);
-    for (void *p : {(void *)h->words, (void *)h->lags, (void *)h->ctxs, (void *)h->totals})
-        if (p) (void)hipHostFree(p);
-    for (hipEvent_t e : {h->ev0, h->ev1})
-        if (e) (void)hipEventDestroy(e);
-    delete h;
-}
+void hq_hb_dev_close(hq_hb_dev *h) { hq::sidecar_close(h); }
 
 int hq_hb_dev_run(hq_hb_dev *h, const hq_dstate_view *st, uint64_t n_member_records, uint64_t n,
                   const uint32_t *groups, hq_heartbeat_output *out, uint32_t *error) {
     hq_ctx *ctx = h->ctx;
     hipStream_t s = ctx->stream;
+    const char *const what = "hq_worker_heartbeats";
     *error = 0;
     int rc = hq::check_hip(ctx, hipSetDevice(ctx->device), "hipSetDevice");
-    if (!rc) rc = grow_pinned(ctx, &h->words, &h->words_cap, n, "hq_heartbeat words");
-    if (!rc) rc = grow_dev(ctx, &h->meta, &h->meta_cap, n, "hq_heartbeat words");
-    if (!rc) rc = grow_dev(ctx, &h->scan, &h->scan_cap, n + 1, "hq_heartbeat scan");
-    if (!rc && groups) rc = grow_dev(ctx, &h->list, &h->list_cap, n, "hq_heartbeat list");
+    if (!rc) rc = h->words.grow(ctx, n, "hq_heartbeat words");
+    if (!rc) rc = h->meta.grow(ctx, n, "hq_heartbeat words");
+    if (!rc) rc = h->scan.grow(ctx, n + 1, "hq_heartbeat scan");
+    if (!rc && groups) rc = h->list.grow(ctx, n, "hq_heartbeat list");
     // (a first call's record buffers: a record for one group in four, grown to what a call needs)
-    if (!rc) rc = grow_pinned(ctx, &h->lags, &h->lag_cap, std::max<uint64_t>(n / 4, 256),
-                              "hq_heartbeat lags");
-    if (!rc) rc = grow_pinned(ctx, &h->ctxs, &h->ctx_cap, std::max<uint64_t>(n / 4, 256),
-                              "hq_heartbeat ctxs");
+    if (!rc) rc = h->lags.grow(ctx, std::max<uint64_t>(n / 4, 256), "hq_heartbeat lags");
+    if (!rc) rc = h->ctxs.grow(ctx, std::max<uint64_t>(n / 4, 256), "hq_heartbeat ctxs");
     if (rc) return rc;
 
+    uint64_t *const n_messages = h->dev + 1;
     HbK k{};
     k.groups = st->groups;
     k.reads = st->reads;
     k.members = st->members;
     k.n_state_groups = st->n_groups;
     k.n_state_members = n_member_records;
-    k.list = groups ? h->list : nullptr;
+    k.list = groups ? h->list.get() : nullptr;
     k.n = n;
     k.words = h->words;
     k.meta = h->meta;
     k.scan = h->scan;
     k.totals = h->totals;
-    k.error = reinterpret_cast<uint32_t *>(h->misc);
-    k.n_messages = h->misc + 1;
+    k.error = h->error();
+    k.n_messages = n_messages;
 
     const hipcub::TransformInputIterator<uint64_t, HbCount, hipcub::CountingInputIterator<uint64_t>>
         counts(hipcub::CountingInputIterator<uint64_t>(0), HbCount{h->meta, n});
@@ -253,35 +186,31 @@ int hq_hb_dev_run(hq_hb_dev *h, const hq_dstate_view *st, uint64_t n_member_reco
         messages(hipcub::CountingInputIterator<uint64_t>(0), HbMessages{h->meta});
     const int items = (int)n;     // (n < 2^28)
     size_t tmp = 0, tmp2 = 0;
-    rc = hq::check_hip(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, counts, h->scan, items + 1, s),
+    rc = hq::check_hip(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, counts, h->scan.get(), items + 1, s),
                        "hipcub scan size");
     if (!rc)
-        rc = hq::check_hip(ctx, hipcub::DeviceReduce::Sum(nullptr, tmp2, messages, h->misc + 1, items, s),
+        rc = hq::check_hip(ctx, hipcub::DeviceReduce::Sum(nullptr, tmp2, messages, n_messages, items, s),
                            "hipcub sum size");
-    tmp = std::max(tmp, tmp2);
-    if (!rc && tmp > h->scan_tmp_cap) {
-        if (h->scan_tmp) (void)hipFree(h->scan_tmp);
-        h->scan_tmp = nullptr;
-        h->scan_tmp_cap = 0;
-        rc = hq::check_hip(ctx, hipMalloc(&h->scan_tmp, tmp + tmp / 2), "hq_heartbeat scan");
-        if (!rc) h->scan_tmp_cap = tmp + tmp / 2;
-    }
-    if (!rc && groups)
+    if (!rc) rc = h->scan_tmp.grow(ctx, std::max(tmp, tmp2), "hq_heartbeat scan");
+    if (rc) return rc;            // (nothing is queued yet; from here on every return is finish's)
+
+    if (groups)
         rc = hq::check_hip(ctx, hipMemcpyAsync(h->list, groups, n * 4, hipMemcpyHostToDevice, s),
                            "hq_heartbeat list");
-    if (!rc) rc = hq::check_hip(ctx, hipMemsetAsync(h->misc, 0, 16, s), "memset");
+    if (!rc) rc = hq::check_hip(ctx, hipMemsetAsync(h->dev, 0, 16, s), "memset");
     if (!rc) rc = hq::check_hip(ctx, hipEventRecord(h->ev0, s), "event");
-    if (rc) return rc;
     const uint32_t g1 = (uint32_t)((n + kBlock - 1) / kBlock), g2 = (uint32_t)(n / kBlock + 1);
-    hipLaunchKernelGGL(k_hb_words, dim3(g1), dim3(kBlock), 0, s, k);
-    rc = hq::check_hip(ctx, hipGetLastError(), "k_hb_words");
     if (!rc) {
-        size_t t = h->scan_tmp_cap;
-        rc = hq::check_hip(ctx, hipcub::DeviceScan::ExclusiveSum(h->scan_tmp, t, counts, h->scan,
+        hipLaunchKernelGGL(k_hb_words, dim3(g1), dim3(kBlock), 0, s, k);
+        rc = hq::check_hip(ctx, hipGetLastError(), "k_hb_words");
+    }
+    if (!rc) {
+        size_t t = h->scan_tmp.cap();
+        rc = hq::check_hip(ctx, hipcub::DeviceScan::ExclusiveSum(h->scan_tmp.get(), t, counts, h->scan.get(),
                                                                   items + 1, s), "hipcub scan");
-        t = h->scan_tmp_cap;      // (the same temporary: the two run one after the other)
+        t = h->scan_tmp.cap();    // (the same temporary: the two run one after the other)
         if (!rc)
-            rc = hq::check_hip(ctx, hipcub::DeviceReduce::Sum(h->scan_tmp, t, messages, h->misc + 1,
+            rc = hq::check_hip(ctx, hipcub::DeviceReduce::Sum(h->scan_tmp.get(), t, messages, n_messages,
                                                               items, s), "hipcub sum");
     }
     // the records; again with larger buffers when a total passed a capacity (nothing was written
@@ -289,29 +218,24 @@ int hq_hb_dev_run(hq_hb_dev *h, const hq_dstate_view *st, uint64_t n_member_reco
     for (int pass = 0; !rc; ++pass) {
         k.lags = h->lags;
         k.ctxs = h->ctxs;
-        k.lag_cap = h->lag_cap;
-        k.ctx_cap = h->ctx_cap;
+        k.lag_cap = h->lags.cap();
+        k.ctx_cap = h->ctxs.cap();
         hipLaunchKernelGGL(k_hb_records, dim3(g2), dim3(kBlock), 0, s, k);
         rc = hq::check_hip(ctx, hipGetLastError(), "k_hb_records");
         if (!rc) rc = hq::check_hip(ctx, hipEventRecord(h->ev1, s), "event");
-        if (!rc) rc = hq::check_hip(ctx, hipStreamSynchronize(s), "hq_worker_heartbeats");
-        if (rc) break;
+        rc = hq::finish(ctx, rc, what);
+        if (rc) return rc;
         if (h->totals[2]) {
             *error = (uint32_t)h->totals[2];
             return HQ_E_INVAL;
         }
-        if (h->totals[0] <= h->lag_cap && h->totals[1] <= h->ctx_cap) break;
+        if (h->totals[0] <= h->lags.cap() && h->totals[1] <= h->ctxs.cap()) break;
         if (pass) return hq::fail(ctx, HQ_E_STATE, "hq_worker_heartbeats: record totals changed");
-        rc = grow_pinned(ctx, &h->lags, &h->lag_cap, h->totals[0], "hq_heartbeat lags");
-        if (!rc) rc = grow_pinned(ctx, &h->ctxs, &h->ctx_cap, h->totals[1], "hq_heartbeat ctxs");
+        rc = h->lags.grow(ctx, h->totals[0], "hq_heartbeat lags");
+        if (!rc) rc = h->ctxs.grow(ctx, h->totals[1], "hq_heartbeat ctxs");
     }
-    if (rc) return rc;
+    if (rc) return hq::finish(ctx, rc, what);
 
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, h->ev0, h->ev1) != hipSuccess) {
-        (void)hipGetLastError();
-        ms = 0.f;
-    }
     out->words = h->words;
     out->n_groups = n;
     out->lags = h->lags;
@@ -319,6 +243,6 @@ int hq_hb_dev_run(hq_hb_dev *h, const hq_dstate_view *st, uint64_t n_member_reco
     out->ctxs = h->ctxs;
     out->n_ctxs = h->totals[1];
     out->n_messages = h->totals[3];
-    out->gpu_ns = (uint64_t)((double)ms * 1e6);
+    out->gpu_ns = hq::elapsed_ns(h->ev0, h->ev1);
     return HQ_OK;
 }

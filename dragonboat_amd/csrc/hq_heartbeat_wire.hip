@@ -30,11 +30,10 @@
 
 #include <algorithm>
 #include <cstring>
-#include <new>
 
 #include "hq_heartbeat.h"
 #include "hq_heartbeat_wire.h"
-#include "hq_internal.h"
+#include "hq_sidecar.h"
 
 namespace {
 
@@ -291,120 +290,51 @@ __global__ void __launch_bounds__(kBlock) k_hbw_encode(HbwK k) {
     }
 }
 
-template <class T>
-int grow_dev(hq_ctx *ctx, T **p, size_t *cap, size_t need, const char *what) {
-    if (need <= *cap) return HQ_OK;
-    const size_t want = need + need / 2;
-    T *n = nullptr;
-    int rc = hq::check_hip(ctx, hipMalloc(reinterpret_cast<void **>(&n), want * sizeof(T)), what);
-    if (rc) return rc;
-    if (*p) (void)hipFree(*p);
-    *p = n;
-    *cap = want;
-    return HQ_OK;
-}
-
-template <class T>
-int grow_pinned(hq_ctx *ctx, T **p, size_t *cap, size_t need, const char *what) {
-    if (need <= *cap) return HQ_OK;
-    const size_t want = need + need / 2;
-    T *n = nullptr;
-    int rc = hq::check_hip(ctx, hipHostMalloc(reinterpret_cast<void **>(&n), want * sizeof(T),
-                                              hipHostMallocDefault), what);
-    if (rc) return rc;
-    if (*p) (void)hipHostFree(*p);
-    *p = n;
-    *cap = want;
-    return HQ_OK;
-}
-
 }  // namespace
 
-struct hq_hbw_dev {
-    hq_ctx *ctx = nullptr;
-    uint16_t *routes = nullptr;    // the route column, 16 per group
-    size_t routes_cap = 0;         // (groups)
-    uint32_t *list = nullptr, *meta = nullptr;
-    uint64_t *scan = nullptr;
-    uint32_t *error = nullptr;
-    uint8_t *source = nullptr;     // kHbSourceMax bytes
-    uint16_t *keys = nullptr;      // 2 m: as written, sorted
-    uint32_t *vals = nullptr, *dstart = nullptr, *sizes = nullptr;
-    uint64_t *bscan = nullptr, *offs = nullptr;
-    void *tmp = nullptr;
-    size_t list_cap = 0, meta_cap = 0, scan_cap = 0, keys_cap = 0, vals_cap = 0, dstart_cap = 0,
-           sizes_cap = 0, bscan_cap = 0, offs_cap = 0, tmp_cap = 0;
-    uint8_t *bytes = nullptr;      // pinned host
-    hq_heartbeat_batch *batches = nullptr;
-    uint64_t *totals = nullptr;
-    size_t bytes_cap = 0, batch_cap = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+struct hq_hbw_dev : hq::Sidecar {
+    hq::DevBuf<RouteRow> routes;       // the route column, a row per group
+    hq::DevBuf<uint32_t> list, meta;
+    hq::DevBuf<uint64_t> scan;
+    hq::DevBuf<uint8_t> source;        // kHbSourceMax bytes
+    hq::DevBuf<uint16_t> keys;         // 2 m: as written, sorted
+    hq::DevBuf<uint32_t> vals, dstart, sizes;
+    hq::DevBuf<uint64_t> bscan, offs;
+    hq::DevBuf<uint8_t> tmp;           // hipcub's temporary
+    hq::PinBuf<uint8_t> bytes;         // pinned host
+    hq::PinBuf<hq_heartbeat_batch> batches;
 };
+static_assert(sizeof(RouteRow) == kDMembers * sizeof(uint16_t), "a row is a group's routes");
 
 int hq_hbw_dev_open(hq_ctx *ctx, hq_hbw_dev **out) {
-    *out = new (std::nothrow) hq_hbw_dev();
-    if (!*out) return HQ_E_NOMEM;
-    hq_hbw_dev *h = *out;
-    h->ctx = ctx;
-    int rc = hq::check_hip(ctx, hipSetDevice(ctx->device), "hipSetDevice");
-    for (hipEvent_t *e : {&h->ev0, &h->ev1})
-        if (!rc) rc = hq::check_hip(ctx, hipEventCreate(e), "event");
-    if (!rc) rc = hq::check_hip(ctx, hipMalloc(reinterpret_cast<void **>(&h->error), 16),
-                                "hq_heartbeat_wire error word");
-    if (!rc) rc = hq::check_hip(ctx, hipMalloc(reinterpret_cast<void **>(&h->source), kHbSourceMax),
-                                "hq_heartbeat_wire source");
-    if (!rc)
-        rc = hq::check_hip(ctx, hipHostMalloc(reinterpret_cast<void **>(&h->totals), 64,
-                                              hipHostMallocDefault), "hq_heartbeat_wire totals");
-    if (!rc) std::memset(h->totals, 0, 64);
-    if (rc) {
-        hq_hbw_dev_close(h);
+    int rc = hq::sidecar_open(ctx, out, "hq_heartbeat_wire");
+    if (!rc && (rc = (*out)->source.reserve(ctx, kHbSourceMax, "hq_heartbeat_wire source"))) {
+        hq_hbw_dev_close(*out);
         *out = nullptr;
     }
     return rc;
 }
 
-void hq_hbw_dev_close(hq_hbw_dev *h) {
-    if (!h) return;
-    (void)hipSetDevice(h->ctx->device);
-    (void)hipStreamSynchronize(h->ctx->stream);
-    for (void *p : {(void *)h->routes, (void *)h->list, (void *)h->meta, (void *)h->scan,
-                    (void *)h->error, (void *)h->source, (void *)h->keys, (void *)h->vals,
-                    (void *)h->dstart, (void *)h->sizes, (void *)h->bscan, (void *)h->offs, h->tmp})
-        if (p) (void)hipFree(p);
-    for (void *p : {(void *)h->bytes, (void *)h->batches, (void *)h->totals})
-        if (p) (void)hipHostFree(p);
-    for (hipEvent_t e : {h->ev0, h->ev1})
-        if (e) (void)hipEventDestroy(e);
-    delete h;
-}
+void hq_hbw_dev_close(hq_hbw_dev *h) { hq::sidecar_close(h); }
 
 int hq_hbw_dev_put_routes(hq_hbw_dev *h, const uint16_t *routes, uint64_t n_groups, uint64_t g0,
                           uint64_t g1) {
     hq_ctx *ctx = h->ctx;
     int rc = hq::check_hip(ctx, hipSetDevice(ctx->device), "hipSetDevice");
     if (rc) return rc;
-    if (n_groups > h->routes_cap) {                   // a new column: every row again
-        const size_t want = n_groups + n_groups / 2;
-        uint16_t *n = nullptr;
-        rc = hq::check_hip(ctx, hipMalloc(reinterpret_cast<void **>(&n), want * kDMembers * 2),
-                           "hq_heartbeat_wire routes");
+    if (n_groups > h->routes.cap()) {                 // a new column: every row again
+        // (no kernel of an earlier call reads the old one: every return has waited for the stream)
+        rc = h->routes.grow(ctx, n_groups, "hq_heartbeat_wire routes");
         if (rc) return rc;
-        // (kernels of an earlier call have finished: every call ends with a synchronize)
-        if (h->routes) (void)hipFree(h->routes);
-        h->routes = n;
-        h->routes_cap = want;
         g0 = 0;
         g1 = n_groups;
     }
     if (g1 > n_groups) g1 = n_groups;
     if (g0 >= g1) return HQ_OK;
-    rc = hq::check_hip(ctx, hipMemcpyAsync(h->routes + g0 * kDMembers, routes + g0 * kDMembers,
-                                           (g1 - g0) * kDMembers * 2, hipMemcpyHostToDevice,
-                                           ctx->stream), "hq_heartbeat_wire routes");
+    rc = hq::check_hip(ctx, hipMemcpyAsync(h->routes + g0, routes + g0 * kDMembers, (g1 - g0) * sizeof(RouteRow),
+                                           hipMemcpyHostToDevice, ctx->stream), "hq_heartbeat_wire routes");
     // (the rows are pageable host memory the caller may change after this returns)
-    if (!rc) rc = hq::check_hip(ctx, hipStreamSynchronize(ctx->stream), "hq_heartbeat_wire routes");
-    return rc;
+    return hq::finish(ctx, rc, "hq_heartbeat_wire routes");
 }
 
 int hq_hbw_dev_run(hq_hbw_dev *h, const hq_dstate_view *st, uint64_t n_member_records, uint64_t n,
@@ -412,17 +342,16 @@ int hq_hbw_dev_run(hq_hbw_dev *h, const hq_dstate_view *st, uint64_t n_member_re
                    hq_heartbeat_batches *out, uint32_t *error) {
     hq_ctx *ctx = h->ctx;
     hipStream_t s = ctx->stream;
+    const char *const what = "hq_worker_heartbeat_batches";
     *error = 0;
-    if (st->n_groups > h->routes_cap)
+    if (st->n_groups > h->routes.cap())
         return hq::fail(ctx, HQ_E_STATE, "hq_worker_heartbeat_batches: the route column is short");
     int rc = hq::check_hip(ctx, hipSetDevice(ctx->device), "hipSetDevice");
-    if (!rc) rc = grow_dev(ctx, &h->meta, &h->meta_cap, n, "hq_heartbeat_wire words");
-    if (!rc) rc = grow_dev(ctx, &h->scan, &h->scan_cap, n + 1, "hq_heartbeat_wire scan");
-    if (!rc && groups) rc = grow_dev(ctx, &h->list, &h->list_cap, n, "hq_heartbeat_wire list");
-    if (!rc) rc = grow_dev(ctx, &h->dstart, &h->dstart_cap, (size_t)cfg->n_dest + 1,
-                           "hq_heartbeat_wire destinations");
-    if (!rc) rc = grow_dev(ctx, &h->bscan, &h->bscan_cap, (size_t)cfg->n_dest + 1,
-                           "hq_heartbeat_wire destinations");
+    if (!rc) rc = h->meta.grow(ctx, n, "hq_heartbeat_wire words");
+    if (!rc) rc = h->scan.grow(ctx, n + 1, "hq_heartbeat_wire scan");
+    if (!rc && groups) rc = h->list.grow(ctx, n, "hq_heartbeat_wire list");
+    if (!rc) rc = h->dstart.grow(ctx, (size_t)cfg->n_dest + 1, "hq_heartbeat_wire destinations");
+    if (!rc) rc = h->bscan.grow(ctx, (size_t)cfg->n_dest + 1, "hq_heartbeat_wire destinations");
     if (rc) return rc;
 
     HbwK k{};
@@ -431,9 +360,9 @@ int hq_hbw_dev_run(hq_hbw_dev *h, const hq_dstate_view *st, uint64_t n_member_re
     k.members = st->members;
     k.n_state_groups = st->n_groups;
     k.n_state_members = n_member_records;
-    k.list = groups ? h->list : nullptr;
+    k.list = groups ? h->list.get() : nullptr;
     k.n = n;
-    k.routes = h->routes;
+    k.routes = reinterpret_cast<const uint16_t *>(h->routes.get());
     k.n_dest = cfg->n_dest;
     k.bm = cfg->batch_messages ? cfg->batch_messages : UINT32_MAX;
     k.deployment_id = cfg->deployment_id;
@@ -442,7 +371,7 @@ int hq_hbw_dev_run(hq_hbw_dev *h, const hq_dstate_view *st, uint64_t n_member_re
     k.trailer_len = hb_trailer_size(cfg->deployment_id, cfg->source_len);
     k.meta = h->meta;
     k.scan = h->scan;
-    k.error = h->error;
+    k.error = h->error();
     k.dstart = h->dstart;
     k.bscan = h->bscan;
     k.totals = h->totals;
@@ -452,42 +381,36 @@ int hq_hbw_dev_run(hq_hbw_dev *h, const hq_dstate_view *st, uint64_t n_member_re
                                                                              HbwCount{h->meta, n});
     const int items = (int)n;     // (n < 2^28)
     const int dests = (int)cfg->n_dest + 1;
-    auto ensure_tmp = [&](size_t need) {
-        if (need <= h->tmp_cap) return (int)HQ_OK;
-        if (h->tmp) (void)hipFree(h->tmp);
-        h->tmp = nullptr;
-        h->tmp_cap = 0;
-        int r = hq::check_hip(ctx, hipMalloc(&h->tmp, need + need / 2), "hq_heartbeat_wire scan");
-        if (!r) h->tmp_cap = need + need / 2;
-        return r;
-    };
     size_t tmp = 0;
-    rc = hq::check_hip(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, counts, h->scan, items + 1, s),
+    rc = hq::check_hip(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, counts, k.scan, items + 1, s),
                        "hipcub scan size");
-    if (!rc) rc = ensure_tmp(tmp);
-    if (!rc && groups)
+    if (!rc) rc = h->tmp.grow(ctx, tmp, "hq_heartbeat_wire scan");
+    if (rc) return rc;            // (nothing is queued yet; from here on every return is finish's)
+
+    if (groups)
         rc = hq::check_hip(ctx, hipMemcpyAsync(h->list, groups, n * 4, hipMemcpyHostToDevice, s),
                            "hq_heartbeat_wire list");
     if (!rc && cfg->source_len)
         rc = hq::check_hip(ctx, hipMemcpyAsync(h->source, cfg->source, cfg->source_len,
                                                hipMemcpyHostToDevice, s), "hq_heartbeat_wire source");
-    if (!rc) rc = hq::check_hip(ctx, hipMemsetAsync(h->error, 0, 16, s), "memset");
+    if (!rc) rc = hq::check_hip(ctx, hipMemsetAsync(h->error(), 0, 16, s), "memset");
     if (!rc) rc = hq::check_hip(ctx, hipEventRecord(h->ev0, s), "event");
-    if (rc) return rc;
     const uint32_t g1 = (uint32_t)((n + kBlock - 1) / kBlock);
-    hipLaunchKernelGGL(k_hbw_words, dim3(g1), dim3(kBlock), 0, s, k);
-    rc = hq::check_hip(ctx, hipGetLastError(), "k_hbw_words");
     if (!rc) {
-        size_t t = h->tmp_cap;
-        rc = hq::check_hip(ctx, hipcub::DeviceScan::ExclusiveSum(h->tmp, t, counts, h->scan, items + 1, s),
+        hipLaunchKernelGGL(k_hbw_words, dim3(g1), dim3(kBlock), 0, s, k);
+        rc = hq::check_hip(ctx, hipGetLastError(), "k_hbw_words");
+    }
+    if (!rc) {
+        size_t t = h->tmp.cap();
+        rc = hq::check_hip(ctx, hipcub::DeviceScan::ExclusiveSum(h->tmp.get(), t, counts, k.scan, items + 1, s),
                            "hipcub scan");
     }
-    if (!rc) rc = hq::check_hip(ctx, hipMemcpyAsync(h->totals, h->scan + n, 8, hipMemcpyDeviceToHost, s),
+    if (!rc) rc = hq::check_hip(ctx, hipMemcpyAsync(h->totals, k.scan + n, 8, hipMemcpyDeviceToHost, s),
                                 "hq_heartbeat_wire totals");
-    if (!rc) rc = hq::check_hip(ctx, hipMemcpyAsync(h->totals + 1, h->error, 4, hipMemcpyDeviceToHost, s),
+    if (!rc) rc = hq::check_hip(ctx, hipMemcpyAsync(h->totals + 1, h->error(), 4, hipMemcpyDeviceToHost, s),
                                 "hq_heartbeat_wire totals");
     // (the list and the source are the caller's memory: they are on the device after this)
-    if (!rc) rc = hq::check_hip(ctx, hipStreamSynchronize(s), "hq_worker_heartbeat_batches");
+    rc = hq::finish(ctx, rc, what);
     if (rc) return rc;
     if ((uint32_t)h->totals[1]) {
         *error = (uint32_t)h->totals[1];
@@ -504,16 +427,15 @@ int hq_hbw_dev_run(hq_hbw_dev *h, const hq_dstate_view *st, uint64_t n_member_re
     const uint64_t batches_max = std::min<uint64_t>(m, (uint64_t)cfg->n_dest + m / k.bm);
     // (the sort's two halves each 16-byte aligned for any m: they start at multiples of 8 items)
     const uint64_t half = (m + 7) & ~uint64_t(7);
-    rc = grow_dev(ctx, &h->keys, &h->keys_cap, 2 * half, "hq_heartbeat_wire keys");
-    if (!rc) rc = grow_dev(ctx, &h->vals, &h->vals_cap, 2 * half, "hq_heartbeat_wire values");
-    if (!rc) rc = grow_dev(ctx, &h->sizes, &h->sizes_cap, m, "hq_heartbeat_wire sizes");
-    if (!rc) rc = grow_dev(ctx, &h->offs, &h->offs_cap, m + 1, "hq_heartbeat_wire offsets");
-    if (!rc) rc = grow_pinned(ctx, &h->batches, &h->batch_cap, batches_max, "hq_heartbeat_wire batches");
+    rc = h->keys.grow(ctx, 2 * half, "hq_heartbeat_wire keys");
+    if (!rc) rc = h->vals.grow(ctx, 2 * half, "hq_heartbeat_wire values");
+    if (!rc) rc = h->sizes.grow(ctx, m, "hq_heartbeat_wire sizes");
+    if (!rc) rc = h->offs.grow(ctx, m + 1, "hq_heartbeat_wire offsets");
+    if (!rc) rc = h->batches.grow(ctx, batches_max, "hq_heartbeat_wire batches");
     // (a first call's bytes: 58 per message and a trailer per destination, grown to what a call needs)
-    if (!rc) rc = grow_pinned(ctx, &h->bytes, &h->bytes_cap,
-                              m * 58 + (uint64_t)std::min<uint64_t>(m, cfg->n_dest) * k.trailer_len,
-                              "hq_heartbeat_wire bytes");
-    if (rc) return rc;
+    if (!rc) rc = h->bytes.grow(ctx, m * 58 + (uint64_t)std::min<uint64_t>(m, cfg->n_dest) * k.trailer_len,
+                                "hq_heartbeat_wire bytes");
+    if (rc) return hq::finish(ctx, rc, what);
     k.m = m;
     k.keys_in = h->keys;
     k.keys = h->keys + half;
@@ -532,19 +454,19 @@ int hq_hbw_dev_run(hq_hbw_dev *h, const hq_dstate_view *st, uint64_t n_member_re
     rc = hq::check_hip(ctx, hipcub::DeviceRadixSort::SortPairs(nullptr, t1, k.keys_in, k.keys, k.vals_in,
                                                                k.vals, (int)m, 0, end_bit, s),
                        "hipcub sort size");
-    if (!rc) rc = hq::check_hip(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, t2, nbatches, h->bscan,
+    if (!rc) rc = hq::check_hip(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, t2, nbatches, k.bscan,
                                                                       dests, s), "hipcub scan size");
-    if (!rc) rc = hq::check_hip(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, t3, sizes, h->offs,
+    if (!rc) rc = hq::check_hip(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, t3, sizes, k.offs,
                                                                       (int)m + 1, s), "hipcub scan size");
-    if (!rc) rc = ensure_tmp(std::max(t1, std::max(t2, t3)));
-    if (rc) return rc;
+    if (!rc) rc = h->tmp.grow(ctx, std::max(t1, std::max(t2, t3)), "hq_heartbeat_wire scan");
+    if (rc) return hq::finish(ctx, rc, what);
 
     const uint32_t gm = (uint32_t)((m + kBlock - 1) / kBlock);
     hipLaunchKernelGGL(k_hbw_desc, dim3(g1), dim3(kBlock), 0, s, k);
     rc = hq::check_hip(ctx, hipGetLastError(), "k_hbw_desc");
     if (!rc) {
-        size_t t = h->tmp_cap;    // (the same temporary: the sort and the scans run one after another)
-        rc = hq::check_hip(ctx, hipcub::DeviceRadixSort::SortPairs(h->tmp, t, k.keys_in, k.keys, k.vals_in,
+        size_t t = h->tmp.cap();  // (the same temporary: the sort and the scans run one after another)
+        rc = hq::check_hip(ctx, hipcub::DeviceRadixSort::SortPairs(h->tmp.get(), t, k.keys_in, k.keys, k.vals_in,
                                                                    k.vals, (int)m, 0, end_bit, s),
                            "hipcub sort");
     }
@@ -554,8 +476,8 @@ int hq_hbw_dev_run(hq_hbw_dev *h, const hq_dstate_view *st, uint64_t n_member_re
         rc = hq::check_hip(ctx, hipGetLastError(), "k_hbw_dests");
     }
     if (!rc) {
-        size_t t = h->tmp_cap;
-        rc = hq::check_hip(ctx, hipcub::DeviceScan::ExclusiveSum(h->tmp, t, nbatches, h->bscan, dests, s),
+        size_t t = h->tmp.cap();
+        rc = hq::check_hip(ctx, hipcub::DeviceScan::ExclusiveSum(h->tmp.get(), t, nbatches, k.bscan, dests, s),
                            "hipcub scan");
     }
     if (!rc) {
@@ -563,8 +485,8 @@ int hq_hbw_dev_run(hq_hbw_dev *h, const hq_dstate_view *st, uint64_t n_member_re
         rc = hq::check_hip(ctx, hipGetLastError(), "k_hbw_sizes");
     }
     if (!rc) {
-        size_t t = h->tmp_cap;
-        rc = hq::check_hip(ctx, hipcub::DeviceScan::ExclusiveSum(h->tmp, t, sizes, h->offs, (int)m + 1, s),
+        size_t t = h->tmp.cap();
+        rc = hq::check_hip(ctx, hipcub::DeviceScan::ExclusiveSum(h->tmp.get(), t, sizes, k.offs, (int)m + 1, s),
                            "hipcub scan");
     }
     // the bytes and the table; again with larger buffers when a total passed a capacity (nothing
@@ -572,30 +494,25 @@ int hq_hbw_dev_run(hq_hbw_dev *h, const hq_dstate_view *st, uint64_t n_member_re
     for (int pass = 0; !rc; ++pass) {
         k.bytes = h->bytes;
         k.batches = h->batches;
-        k.bytes_cap = h->bytes_cap;
-        k.batch_cap = h->batch_cap;
+        k.bytes_cap = h->bytes.cap();
+        k.batch_cap = h->batches.cap();
         hipLaunchKernelGGL(k_hbw_encode, dim3(gm), dim3(kBlock), 0, s, k);
         rc = hq::check_hip(ctx, hipGetLastError(), "k_hbw_encode");
         if (!rc) rc = hq::check_hip(ctx, hipEventRecord(h->ev1, s), "event");
-        if (!rc) rc = hq::check_hip(ctx, hipStreamSynchronize(s), "hq_worker_heartbeat_batches");
-        if (rc) break;
-        if (h->totals[4] <= h->bytes_cap && h->totals[5] <= h->batch_cap) break;
+        rc = hq::finish(ctx, rc, what);
+        if (rc) return rc;
+        if (h->totals[4] <= h->bytes.cap() && h->totals[5] <= h->batches.cap()) break;
         if (pass) return hq::fail(ctx, HQ_E_STATE, "hq_worker_heartbeat_batches: totals changed");
-        rc = grow_pinned(ctx, &h->bytes, &h->bytes_cap, h->totals[4], "hq_heartbeat_wire bytes");
-        if (!rc) rc = grow_pinned(ctx, &h->batches, &h->batch_cap, h->totals[5], "hq_heartbeat_wire batches");
+        rc = h->bytes.grow(ctx, h->totals[4], "hq_heartbeat_wire bytes");
+        if (!rc) rc = h->batches.grow(ctx, h->totals[5], "hq_heartbeat_wire batches");
     }
-    if (rc) return rc;
+    if (rc) return hq::finish(ctx, rc, what);
 
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, h->ev0, h->ev1) != hipSuccess) {
-        (void)hipGetLastError();
-        ms = 0.f;
-    }
     out->bytes = h->bytes;
     out->n_bytes = h->totals[4];
     out->batches = h->batches;
     out->n_batches = h->totals[5];
     out->n_messages = m;
-    out->gpu_ns = (uint64_t)((double)ms * 1e6);
+    out->gpu_ns = hq::elapsed_ns(h->ev0, h->ev1);
     return HQ_OK;
 }

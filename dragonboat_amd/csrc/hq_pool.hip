@@ -16,10 +16,8 @@
 // lane's loads are issued before its first store. No spinning, no LDS, no loops.
 #include <hip/hip_runtime.h>
 
-#include <new>
-
-#include "hq_internal.h"
 #include "hq_pool.h"
+#include "hq_sidecar.h"
 
 namespace {
 
@@ -71,69 +69,21 @@ __global__ void __launch_bounds__(kBlock) k_pool_compact(PoolK k) {
     if (l == 0) k.groups[h].mem = to;
 }
 
-template <class T>
-int grow_pinned(hq_ctx *ctx, T **p, size_t *cap, size_t need, const char *what) {
-    if (need <= *cap) return HQ_OK;
-    const size_t want = (need + need / 2 + 63) / 64 * 64;
-    T *n = nullptr;
-    int rc = hq::check_hip(ctx, hipHostMalloc(reinterpret_cast<void **>(&n), want * sizeof(T),
-                                              hipHostMallocDefault), what);
-    if (rc) return rc;
-    if (*p) (void)hipHostFree(*p);
-    *p = n;
-    *cap = want;
-    return HQ_OK;
-}
-
 }  // namespace
 
-struct hq_pool_dev {
-    hq_ctx *ctx = nullptr;
-    uint32_t *new_mem_host = nullptr;  // pinned staging of the column
-    uint32_t *new_mem = nullptr;       // device
-    uint32_t *error = nullptr;         // device
-    uint32_t *error_host = nullptr;    // pinned
-    size_t host_cap = 0, dev_cap = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+struct hq_pool_dev : hq::Sidecar {     // (totals: the error word as the host reads it)
+    hq::PinBuf<uint32_t> new_mem_host; // pinned staging of the column
+    hq::DevBuf<uint32_t> new_mem;      // device, of new_mem_host's capacity
 };
 
-int hq_pool_dev_open(hq_ctx *ctx, hq_pool_dev **out) {
-    *out = new (std::nothrow) hq_pool_dev();
-    if (!*out) return HQ_E_NOMEM;
-    hq_pool_dev *c = *out;
-    c->ctx = ctx;
-    int rc = hq::check_hip(ctx, hipSetDevice(ctx->device), "hipSetDevice");
-    for (hipEvent_t *e : {&c->ev0, &c->ev1})
-        if (!rc) rc = hq::check_hip(ctx, hipEventCreate(e), "event");
-    if (!rc) rc = hq::check_hip(ctx, hipMalloc(reinterpret_cast<void **>(&c->error), 16),
-                                "hq_pool error word");
-    if (!rc)
-        rc = hq::check_hip(ctx, hipHostMalloc(reinterpret_cast<void **>(&c->error_host), 64,
-                                              hipHostMallocDefault), "hq_pool error word");
-    if (rc) {
-        hq_pool_dev_close(c);
-        *out = nullptr;
-    }
-    return rc;
-}
+int hq_pool_dev_open(hq_ctx *ctx, hq_pool_dev **out) { return hq::sidecar_open(ctx, out, "hq_pool error word"); }
 
-void hq_pool_dev_close(hq_pool_dev *c) {
-    if (!c) return;
-    (void)hipSetDevice(c->ctx->device);
-    (void)hipStreamSynchronize(c->ctx->stream);
-    for (void *p : {(void *)c->new_mem, (void *)c->error})
-        if (p) (void)hipFree(p);
-    for (void *p : {(void *)c->new_mem_host, (void *)c->error_host})
-        if (p) (void)hipHostFree(p);
-    for (hipEvent_t e : {c->ev0, c->ev1})
-        if (e) (void)hipEventDestroy(e);
-    delete c;
-}
+void hq_pool_dev_close(hq_pool_dev *c) { hq::sidecar_close(c); }
 
 int hq_pool_dev_stage(hq_pool_dev *c, uint64_t n_groups, uint32_t **new_mem) {
     hq_ctx *ctx = c->ctx;
     int rc = hq::check_hip(ctx, hipSetDevice(ctx->device), "hipSetDevice");
-    if (!rc) rc = grow_pinned(ctx, &c->new_mem_host, &c->host_cap, n_groups, "hq_pool column");
+    if (!rc) rc = c->new_mem_host.grow(ctx, n_groups, "hq_pool column", hq::Headroom::kHalf64);
     if (rc) return rc;
     *new_mem = c->new_mem_host;
     return HQ_OK;
@@ -146,18 +96,10 @@ int hq_pool_dev_compact(hq_pool_dev *c, const hq_dstate_mut *st, uint64_t n_old,
     const uint64_t G = st->n_groups;
     *error = 0;
     *gpu_ns = 0;
-    if (G == 0 || G > c->host_cap || !dst || !st->groups || !st->members) return HQ_E_INVAL;
+    if (G == 0 || G > c->new_mem_host.cap() || !dst || !st->groups || !st->members) return HQ_E_INVAL;
     if ((G + kGroupsPerBlock - 1) / kGroupsPerBlock > 0x7FFFFFFFull) return HQ_E_INVAL;
     int rc = hq::check_hip(ctx, hipSetDevice(ctx->device), "hipSetDevice");
-    if (!rc && G > c->dev_cap) {
-        uint32_t *p = nullptr;
-        rc = hq::check_hip(ctx, hipMalloc(reinterpret_cast<void **>(&p), c->host_cap * 4), "hq_pool column");
-        if (!rc) {
-            if (c->new_mem) (void)hipFree(c->new_mem);
-            c->new_mem = p;
-            c->dev_cap = c->host_cap;
-        }
-    }
+    if (!rc && G > c->new_mem.cap()) rc = c->new_mem.reserve(ctx, c->new_mem_host.cap(), "hq_pool column");
     if (rc) return rc;
 
     PoolK k{};
@@ -168,32 +110,29 @@ int hq_pool_dev_compact(hq_pool_dev *c, const hq_dstate_mut *st, uint64_t n_old,
     k.n_groups = G;
     k.n_old = n_old;
     k.n_new = n_new;
-    k.error = c->error;
+    k.error = c->error();
 
+    // (from here on every return is finish's: the staging is rewritten by the next call)
     rc = hq::check_hip(ctx, hipEventRecord(c->ev0, s), "event");
-    if (!rc) rc = hq::check_hip(ctx, hipMemsetAsync(c->error, 0, 16, s), "memset");
+    if (!rc) rc = hq::check_hip(ctx, hipMemsetAsync(c->error(), 0, 16, s), "memset");
     if (!rc)
         rc = hq::check_hip(ctx, hipMemcpyAsync(c->new_mem, c->new_mem_host, G * 4, hipMemcpyHostToDevice, s),
                            "hq_pool column");
-    if (rc) return rc;
-    const uint32_t grid = (uint32_t)((G + kGroupsPerBlock - 1) / kGroupsPerBlock);
-    hipLaunchKernelGGL(k_pool_compact, dim3(grid), dim3(kBlock), 0, s, k);
-    rc = hq::check_hip(ctx, hipGetLastError(), "k_pool_compact");
+    if (!rc) {
+        const uint32_t grid = (uint32_t)((G + kGroupsPerBlock - 1) / kGroupsPerBlock);
+        hipLaunchKernelGGL(k_pool_compact, dim3(grid), dim3(kBlock), 0, s, k);
+        rc = hq::check_hip(ctx, hipGetLastError(), "k_pool_compact");
+    }
     if (!rc)
-        rc = hq::check_hip(ctx, hipMemcpyAsync(c->error_host, c->error, 4, hipMemcpyDeviceToHost, s),
+        rc = hq::check_hip(ctx, hipMemcpyAsync(c->totals, c->error(), 4, hipMemcpyDeviceToHost, s),
                            "hq_pool error word");
     if (!rc) rc = hq::check_hip(ctx, hipEventRecord(c->ev1, s), "event");
-    if (!rc) rc = hq::check_hip(ctx, hipStreamSynchronize(s), "hq_pool");
+    rc = hq::finish(ctx, rc, "hq_pool");
     if (rc) return rc;
-    if (*c->error_host) {
-        *error = *c->error_host;
+    if ((uint32_t)c->totals[0]) {
+        *error = (uint32_t)c->totals[0];
         return HQ_E_INVAL;
     }
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, c->ev0, c->ev1) != hipSuccess) {
-        (void)hipGetLastError();
-        ms = 0.f;
-    }
-    *gpu_ns = (uint64_t)((double)ms * 1e6);
+    *gpu_ns = hq::elapsed_ns(c->ev0, c->ev1);
     return HQ_OK;
 }

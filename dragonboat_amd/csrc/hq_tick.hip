@@ -24,9 +24,8 @@
 
 #include <algorithm>
 #include <cstring>
-#include <new>
 
-#include "hq_internal.h"
+#include "hq_sidecar.h"
 #include "hq_tick.h"
 
 namespace {
@@ -51,17 +50,15 @@ __device__ __forceinline__ Word pack(const hq_tick_timer &t) {
     return w;
 }
 
-// what the timers read of a group record: its second and fourth 16 bytes
+// what the timers read of a group record (hq_dgroup_load, hq_dstep.h)
 struct GroupRef {
     uint64_t term;
     uint32_t state;
     bool suspended;
 };
 __device__ __forceinline__ GroupRef load_group(const hq_dgroup *g) {
-    const uint4 *p = reinterpret_cast<const uint4 *>(g);
-    const uint4 b = p[1], d = p[3];                  // term, committed | mem, 8 bytes, pad1
-    return GroupRef{(uint64_t)b.x | (uint64_t)b.y << 32, (d.y >> 16) & 0xFFu,
-                    (((d.z >> 8) & 0xFFu) & kDSuspended) != 0};
+    const hq_dgroup_fields f = hq_dgroup_load(g);
+    return GroupRef{f.term, f.state, (f.flags & kDSuspended) != 0};
 }
 __device__ __forceinline__ uint64_t load_cluster_id(const hq_dgroup *g) {
     return *reinterpret_cast<const uint64_t *>(g);
@@ -215,113 +212,31 @@ __global__ void __launch_bounds__(kBlock) k_tick_set(ListedK k) {
     if (k.pending) atomicAnd(k.pending + (h >> 5), ~(1u << (h & 31u)));
 }
 
-template <class T>
-int grow_dev(hq_ctx *ctx, T **p, size_t *cap, size_t need, const char *what) {
-    if (need <= *cap) return HQ_OK;
-    const size_t want = need + need / 2;
-    T *n = nullptr;
-    int rc = hq::check_hip(ctx, hipMalloc(reinterpret_cast<void **>(&n), want * sizeof(T)), what);
-    if (rc) return rc;
-    if (*p) (void)hipFree(*p);
-    *p = n;
-    *cap = want;
-    return HQ_OK;
-}
-
-template <class T>
-int grow_pinned(hq_ctx *ctx, T **p, size_t *cap, size_t need, const char *what) {
-    if (need <= *cap) return HQ_OK;
-    const size_t want = need + need / 2;
-    T *n = nullptr;
-    int rc = hq::check_hip(ctx, hipHostMalloc(reinterpret_cast<void **>(&n), want * sizeof(T),
-                                              hipHostMallocDefault), what);
-    if (rc) return rc;
-    if (*p) (void)hipHostFree(*p);
-    *p = n;
-    *cap = want;
-    return HQ_OK;
-}
-
-// The stream waited for whatever `rc` says: nothing of a call stays queued behind its return.
-int finish(hq_ctx *ctx, int rc, const char *what) {
-    if (rc) {
-        (void)hipStreamSynchronize(ctx->stream);     // (rc's message stands)
-        return rc;
-    }
-    return hq::check_hip(ctx, hipStreamSynchronize(ctx->stream), what);
-}
-
-float elapsed_ms(hipEvent_t a, hipEvent_t b) {
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, a, b) != hipSuccess) {
-        (void)hipGetLastError();
-        ms = 0.f;
-    }
-    return ms;
-}
-
 }  // namespace
 
-struct hq_tick_dev {
-    hq_ctx *ctx = nullptr;
-    Word *timers = nullptr;            // device [timers_cap]; the first n_timers are in use
-    size_t timers_cap = 0, n_timers = 0;
-    uint32_t *contact = nullptr;       // device bitmap
-    uint64_t *ballots = nullptr;
-    uint32_t *counts = nullptr, *bases = nullptr;
-    uint32_t *handles = nullptr;       // device: a call's listed handles
-    hq_timer *pub = nullptr;           // device: a call's public timers
-    uint32_t *error = nullptr;         // device
-    size_t contact_cap = 0, ballots_cap = 0, counts_cap = 0, bases_cap = 0, handles_cap = 0, pub_cap = 0;
-    uint32_t *contact_host = nullptr;  // pinned bitmap, zero between calls
-    size_t contact_host_cap = 0;
-    uint32_t *lists[kTickLists] = {nullptr, nullptr, nullptr};   // pinned
-    size_t lists_cap[kTickLists] = {0, 0, 0};
-    uint64_t *totals = nullptr;        // pinned: the four totals, the error word
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+struct hq_tick_dev : hq::Sidecar {     // (totals: the four totals, then the listed calls' error word)
+    hq::DevBuf<Word> timers;           // device; the first n_timers are in use
+    size_t n_timers = 0;
+    hq::DevBuf<uint32_t> contact;      // device bitmap
+    hq::DevBuf<uint64_t> ballots;
+    hq::DevBuf<uint32_t> counts, bases;
+    hq::DevBuf<uint32_t> handles;      // device: a call's listed handles
+    hq::DevBuf<hq_timer> pub;          // device: a call's public timers
+    hq::PinBuf<uint32_t> contact_host; // pinned bitmap, zero between calls
+    hq::PinBuf<uint32_t> lists[kTickLists];   // pinned
 };
 
-int hq_tick_dev_open(hq_ctx *ctx, hq_tick_dev **out) {
-    *out = new (std::nothrow) hq_tick_dev();
-    if (!*out) return HQ_E_NOMEM;
-    hq_tick_dev *t = *out;
-    t->ctx = ctx;
-    int rc = hq::check_hip(ctx, hipSetDevice(ctx->device), "hipSetDevice");
-    for (hipEvent_t *e : {&t->ev0, &t->ev1})
-        if (!rc) rc = hq::check_hip(ctx, hipEventCreate(e), "event");
-    if (!rc) rc = hq::check_hip(ctx, hipMalloc(reinterpret_cast<void **>(&t->error), 16), "hq_tick error word");
-    if (!rc)
-        rc = hq::check_hip(ctx, hipHostMalloc(reinterpret_cast<void **>(&t->totals), 64, hipHostMallocDefault),
-                           "hq_tick totals");
-    if (rc) {
-        hq_tick_dev_close(t);
-        *out = nullptr;
-    }
-    return rc;
-}
+int hq_tick_dev_open(hq_ctx *ctx, hq_tick_dev **out) { return hq::sidecar_open(ctx, out, "hq_tick"); }
 
-void hq_tick_dev_close(hq_tick_dev *t) {
-    if (!t) return;
-    (void)hipSetDevice(t->ctx->device);
-    (void)hipStreamSynchronize(t->ctx->stream);
-    for (void *p : {(void *)t->timers, (void *)t->contact, (void *)t->ballots, (void *)t->counts, (void *)t->bases,
-                    (void *)t->handles, (void *)t->pub, (void *)t->error})
-        if (p) (void)hipFree(p);
-    for (void *p : {(void *)t->contact_host, (void *)t->lists[0], (void *)t->lists[1], (void *)t->lists[2],
-                    (void *)t->totals})
-        if (p) (void)hipHostFree(p);
-    for (hipEvent_t e : {t->ev0, t->ev1})
-        if (e) (void)hipEventDestroy(e);
-    delete t;
-}
+void hq_tick_dev_close(hq_tick_dev *t) { hq::sidecar_close(t); }
 
 int hq_tick_dev_contact(hq_tick_dev *t, uint64_t n_groups, uint32_t **bitmap) {
     hq_ctx *ctx = t->ctx;
     const size_t words = hq::words32(n_groups);
     int rc = hq::check_hip(ctx, hipSetDevice(ctx->device), "hipSetDevice");
-    if (!rc && words > t->contact_host_cap) {
-        rc = grow_pinned(ctx, &t->contact_host, &t->contact_host_cap, words, "hq_tick contact bitmap");
-        if (!rc) std::memset(t->contact_host, 0, t->contact_host_cap * sizeof(uint32_t));
+    if (!rc && words > t->contact_host.cap()) {
+        rc = t->contact_host.grow(ctx, words, "hq_tick contact bitmap");
+        if (!rc) std::memset(t->contact_host, 0, t->contact_host.cap() * sizeof(uint32_t));
     }
     if (rc) return rc;
     *bitmap = t->contact_host;
@@ -335,35 +250,18 @@ int hq_tick_dev_invalidate(hq_tick_dev *t, uint64_t n_groups, bool all, uint64_t
     if (n > 0xFFFFFFFFull || (n && !handles)) return HQ_E_INVAL;
     int rc = hq::check_hip(ctx, hipSetDevice(ctx->device), "hipSetDevice");
     if (rc) return rc;
-    if (n_groups > t->timers_cap) {
-        // a larger array, all unseen, with the old timers copied in (the copy is waited for before
-        // the old array goes)
-        const size_t want = n_groups + n_groups / 2;
-        Word *p = nullptr;
-        rc = hq::check_hip(ctx, hipMalloc(reinterpret_cast<void **>(&p), want * sizeof(Word)), "hq_tick timers");
-        if (rc) return rc;
-        rc = hq::check_hip(ctx, hipMemsetAsync(p, 0xFF, want * sizeof(Word), s), "hq_tick timers");
-        if (!rc && t->n_timers)
-            rc = hq::check_hip(ctx, hipMemcpyAsync(p, t->timers, t->n_timers * sizeof(Word),
-                                                   hipMemcpyDeviceToDevice, s), "hq_tick timers");
-        rc = finish(ctx, rc, "hq_tick timers");
-        if (rc) {
-            (void)hipFree(p);
-            return rc;
-        }
-        if (t->timers) (void)hipFree(t->timers);
-        t->timers = p;
-        t->timers_cap = want;
-    }
+    // a larger array is all unseen, with the old timers copied in
+    rc = t->timers.grow_keep(ctx, n_groups, t->n_timers, 0xFF, "hq_tick timers");
+    if (rc) return rc;
     // (the records between n_timers and the capacity are unseen since the array was made)
     t->n_timers = std::max<size_t>(t->n_timers, n_groups);
     if (all) {
         if (t->n_timers)
             rc = hq::check_hip(ctx, hipMemsetAsync(t->timers, 0xFF, t->n_timers * sizeof(Word), s), "hq_tick timers");
-        return rc ? finish(ctx, rc, "hq_tick timers") : HQ_OK;
+        return rc ? hq::finish(ctx, rc, "hq_tick timers") : HQ_OK;
     }
     if (n == 0) return HQ_OK;
-    rc = grow_dev(ctx, &t->handles, &t->handles_cap, n, "hq_tick handles");
+    rc = t->handles.grow(ctx, n, "hq_tick handles");
     if (rc) return rc;
     rc = hq::check_hip(ctx, hipMemcpyAsync(t->handles, handles, n * 4, hipMemcpyHostToDevice, s), "hq_tick handles");
     if (!rc) {
@@ -375,7 +273,7 @@ int hq_tick_dev_invalidate(hq_tick_dev *t, uint64_t n_groups, bool all, uint64_t
         hipLaunchKernelGGL(k_tick_invalidate, dim3((uint32_t)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, k);
         rc = hq::check_hip(ctx, hipGetLastError(), "k_tick_invalidate");
     }
-    return rc ? finish(ctx, rc, "hq_tick timers") : HQ_OK;
+    return rc ? hq::finish(ctx, rc, "hq_tick timers") : HQ_OK;
 }
 
 int hq_tick_dev_run(hq_tick_dev *t, const hq_dstate_view *st, const hq_tick_params *p, bool with_contact,
@@ -386,34 +284,34 @@ int hq_tick_dev_run(hq_tick_dev *t, const hq_dstate_view *st, const hq_tick_para
     std::memset(out, 0, sizeof *out);
     if (n > t->n_timers || n > 0xFFFFFFFFull) return hq::fail(ctx, HQ_E_STATE, "hq_tick: fewer timers than groups (internal)");
     const size_t cwords = hq::words32(n);
-    if (with_contact && cwords > t->contact_host_cap)
+    if (with_contact && cwords > t->contact_host.cap())
         return hq::fail(ctx, HQ_E_STATE, "hq_tick: the contact bitmap was not staged (internal)");
     if (n == 0) return HQ_OK;
     const uint64_t n_tiles = (n + kBlock - 1) / kBlock;
     int rc = hq::check_hip(ctx, hipSetDevice(ctx->device), "hipSetDevice");
-    if (!rc) rc = grow_dev(ctx, &t->ballots, &t->ballots_cap, n_tiles * kWaves * kBits, "hq_tick ballots");
-    if (!rc) rc = grow_dev(ctx, &t->counts, &t->counts_cap, n_tiles * kBits, "hq_tick counts");
-    if (!rc) rc = grow_dev(ctx, &t->bases, &t->bases_cap, n_tiles * kBits, "hq_tick bases");
-    if (!rc && with_contact) rc = grow_dev(ctx, &t->contact, &t->contact_cap, cwords, "hq_tick contact bitmap");
+    if (!rc) rc = t->ballots.grow(ctx, n_tiles * kWaves * kBits, "hq_tick ballots");
+    if (!rc) rc = t->counts.grow(ctx, n_tiles * kBits, "hq_tick counts");
+    if (!rc) rc = t->bases.grow(ctx, n_tiles * kBits, "hq_tick bases");
+    if (!rc && with_contact) rc = t->contact.grow(ctx, cwords, "hq_tick contact bitmap");
     // (every handle may be due: a list holds them all)
     for (uint32_t c = 0; c < kTickLists && !rc; ++c)
-        rc = grow_pinned(ctx, &t->lists[c], &t->lists_cap[c], n, "hq_tick lists");
+        rc = t->lists[c].grow(ctx, n, "hq_tick lists");
 
     TickK k{};
     k.groups = st->groups;
     k.n = n;
     k.timers = t->timers;
-    k.contact = with_contact ? t->contact : nullptr;
+    k.contact = with_contact ? t->contact.get() : nullptr;
     k.pending = pending;
     k.p = *p;
     k.ballots = t->ballots;
     k.counts = t->counts;
     k.bases = t->bases;
     k.n_tiles = n_tiles;
-    k.list_cap = t->lists_cap[0];
+    k.list_cap = t->lists[0].cap();
     for (uint32_t c = 0; c < kTickLists; ++c) {
         k.lists[c] = t->lists[c];
-        k.list_cap = std::min<uint64_t>(k.list_cap, t->lists_cap[c]);
+        k.list_cap = std::min<uint64_t>(k.list_cap, t->lists[c].cap());
     }
     k.totals = t->totals;
 
@@ -440,7 +338,7 @@ int hq_tick_dev_run(hq_tick_dev *t, const hq_dstate_view *st, const hq_tick_para
         if (!rc && pending) rc = hq::check_hip(ctx, hipMemsetAsync(pending, 0, cwords * 4, s), "hq_tick contacts");
         if (!rc) rc = hq::check_hip(ctx, hipEventRecord(t->ev1, s), "event");
     }
-    if (queued) rc = finish(ctx, rc, "hq_worker_tick");
+    if (queued) rc = hq::finish(ctx, rc, "hq_worker_tick");
     if (with_contact) std::memset(t->contact_host, 0, cwords * 4);   // (consumed, or the call failed)
     if (rc) return rc;
     out->check_quorum = t->lists[0];
@@ -450,7 +348,7 @@ int hq_tick_dev_run(hq_tick_dev *t, const hq_dstate_view *st, const hq_tick_para
     out->election = t->lists[2];
     out->n_election = t->totals[2];
     out->n_ticked = t->totals[3];
-    out->gpu_ns = (uint64_t)((double)elapsed_ms(t->ev0, t->ev1) * 1e6);
+    out->gpu_ns = hq::elapsed_ns(t->ev0, t->ev1);
     return HQ_OK;
 }
 
@@ -467,8 +365,8 @@ int listed(hq_tick_dev *t, int direction, const hq_dstate_view *st, const hq_tic
     if (n == 0 || n > 0xFFFFFFFFull || !host) return HQ_E_INVAL;
     if (st->n_groups > t->n_timers) return hq::fail(ctx, HQ_E_STATE, "hq_tick: fewer timers than groups (internal)");
     int rc = hq::check_hip(ctx, hipSetDevice(ctx->device), "hipSetDevice");
-    if (!rc && handles) rc = grow_dev(ctx, &t->handles, &t->handles_cap, n, "hq_tick handles");
-    if (!rc) rc = grow_dev(ctx, &t->pub, &t->pub_cap, n, "hq_tick timers");
+    if (!rc && handles) rc = t->handles.grow(ctx, n, "hq_tick handles");
+    if (!rc) rc = t->pub.grow(ctx, n, "hq_tick timers");
     if (rc) return rc;
 
     ListedK k{};
@@ -476,13 +374,13 @@ int listed(hq_tick_dev *t, int direction, const hq_dstate_view *st, const hq_tic
     k.n_state_groups = st->n_groups;
     k.timers = t->timers;
     k.p = *p;
-    k.handles = handles ? t->handles : nullptr;
+    k.handles = handles ? t->handles.get() : nullptr;
     k.n = n;
     k.pub = t->pub;
-    k.error = t->error;
+    k.error = t->error();
     k.pending = pending;
 
-    rc = hq::check_hip(ctx, hipMemsetAsync(t->error, 0, 16, s), "memset");
+    rc = hq::check_hip(ctx, hipMemsetAsync(t->error(), 0, 16, s), "memset");
     if (!rc && handles)
         rc = hq::check_hip(ctx, hipMemcpyAsync(t->handles, handles, n * 4, hipMemcpyHostToDevice, s), what);
     if (!rc && direction == kSet)
@@ -495,8 +393,8 @@ int listed(hq_tick_dev *t, int direction, const hq_dstate_view *st, const hq_tic
     }
     // (the error word through the totals' pinned block: its fifth word)
     if (!rc)
-        rc = hq::check_hip(ctx, hipMemcpyAsync(t->totals + kBits, t->error, 4, hipMemcpyDeviceToHost, s), what);
-    rc = finish(ctx, rc, what);
+        rc = hq::check_hip(ctx, hipMemcpyAsync(t->totals + kBits, t->error(), 4, hipMemcpyDeviceToHost, s), what);
+    rc = hq::finish(ctx, rc, what);
     if (rc) return rc;
     if ((uint32_t)t->totals[kBits]) {
         *error = (uint32_t)t->totals[kBits];
@@ -504,7 +402,7 @@ int listed(hq_tick_dev *t, int direction, const hq_dstate_view *st, const hq_tic
     }
     if (direction == kGet) {
         rc = hq::check_hip(ctx, hipMemcpyAsync(host, t->pub, n * sizeof(hq_timer), hipMemcpyDeviceToHost, s), what);
-        rc = finish(ctx, rc, what);
+        rc = hq::finish(ctx, rc, what);
     }
     return rc;
 }

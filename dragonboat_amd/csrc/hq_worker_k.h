@@ -13,6 +13,14 @@
 // All of them plain C++ (no HIP headers): the worker is a client of the same ABI a cgo binding
 // would use. Every C entry's body runs inside `guarded` (hq_guard.h).
 //
+// A device worker's calls beside the step each have a device module behind an opaque struct
+// (hq_hb_dev, hq_hbw_dev, hq_cfg_dev, hq_groups_dev, hq_pool_dev, hq_tick_dev, hq_hbr_dev: kernels
+// and their buffers in the .hip file of the same name). The modules share one scaffold,
+// hq_sidecar.h: owning buffers, one open and one close, and one rule that the worker relies on:
+// nothing of a call stays queued behind its return, whatever it returns (but a successful
+// hq_tick_dev_invalidate, which the tick, get or set after tick_flush is queued behind). So a list,
+// a config or a staging buffer handed to hq_*_dev_* is the caller's again when the call is back.
+//
 // Storage is flat: one fixed-size record per group, its members in one pool (voting slots
 // first, in slot order, so packing a group's match row is a contiguous copy) and pending
 // ReadIndex queues in a pool of fixed 8-entry blocks.
